@@ -5,7 +5,11 @@ One "step" = one full V-cycle (12 levels, V(1,1), the reference's MultiGrid.Step
 fused HIP kernels on a 4097 x 4097 fp64 Poisson problem resident in HBM (synthetic seeded
 right-hand side, zero initial guess), replayed as a HIP graph.  value = B * N^2 * ranks / t_step.
 
-Also reported on the same JSON line:
+A plain run does only that: set up, warm up, time --steps cycles in one call, write the iterate they ended on if
+--dump-outputs DIR is given (DIR/solution.npy, see dump_outputs), print the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the configuration).
+
+With --full, measured in runs of their own after the timed steps and reported on the same JSON line:
   roofline      the DOMINANT kernel of the timed region: fea_mg_cycle_join on the finest level (every
                 boundary between two V-cycles: post-sweep of cycle k + pre-sweep, residual and
                 restriction of cycle k+1; 28 B per fine node, ~45 % of a V-cycle), timed INSIDE the
@@ -517,15 +521,36 @@ DD_MODES = [("segments", False, False, False), ("segments+overlap_l0", False, Tr
             ("captured+overlap_l0", True, True, False), ("captured+split_join", True, False, True)]
 
 
+def warmup_call_cycles(s, steps):
+    """Cycles per warm-up call: the smallest call that visits the HIP graphs vcycle(steps) replays.  The pipelined
+    single-GPU solver replays vcycle(k) as blocks of G joined cycles plus one block of the k % G left over
+    (MultigridSolver.pipe_blocks), each a graph keyed by (start buffer, block size); G is even, so a call of one
+    G-block plus the same remainder starts every block on the same buffer and ends on the same one as vcycle(steps):
+    same graphs, same state, without running all `steps` cycles six times over.  Every other solver: `steps`."""
+    pipe = getattr(s, "pipe_blocks", None)
+    if pipe is None or not s._joinable() or getattr(s, "_hjac_first", False):
+        return steps
+    G = 1 << (max(1, s.GRAPH_CYCLES).bit_length() - 1)
+    if G < 2 or steps < 2 * G:
+        return steps
+    blocks, short = pipe(steps, G), pipe(G + steps % G, G)
+    n = len(blocks) - len(short)  # the short call must drop leading G-blocks only (tools/lab patches pipe_blocks)
+    if n > 0 and blocks[n:] == short and all(b == G for b in blocks[:n]):
+        return G + steps % G
+    return steps
+
+
 def time_steps(s, steps, warmup, ws):
-    """The contract's timing: warm-up calls of the timed call itself (vcycle(steps)), so that every graph the timed
-    call replays (its blocks of joined cycles, keyed by start buffer and size; 6 calls cover every step count) has
-    run once eagerly and been captured before the clock starts — at least `warmup` cycles; then barrier +
-    synchronize, ONE vcycle(steps), synchronize + barrier, max over ranks.  Returns (seconds, warm-up cycles run)."""
-    calls = max(6, -(-warmup // steps))
+    """The contract's timing: warm-up calls that replay the graphs of the timed call (vcycle(steps); see
+    warmup_call_cycles), so that every graph the timed call replays (its blocks of joined cycles, keyed by start
+    buffer and size; 6 calls cover every step count) has run once eagerly and been captured before the clock
+    starts — at least `warmup` cycles; then barrier + synchronize, ONE vcycle(steps), synchronize + barrier, max
+    over ranks.  Returns (seconds, warm-up cycles run)."""
+    per_call = warmup_call_cycles(s, steps)
+    calls = max(6, -(-warmup // per_call))
     calls += calls % 2
     for _ in range(calls):
-        s.vcycle(steps)
+        s.vcycle(per_call)
     torch.cuda.synchronize()
     barrier(ws)
     torch.cuda.synchronize()
@@ -534,7 +559,35 @@ def time_steps(s, steps, warmup, ws):
     torch.cuda.synchronize()
     barrier(ws)
     torch.cuda.synchronize()
-    return max_over_ranks(time.perf_counter() - t0, ws), calls * steps
+    return max_over_ranks(time.perf_counter() - t0, ws), calls * per_call
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 32 MB of float64, well inside the 64 MB a dump may hold
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write what the timed path computed in its last step as DIR/<name>.npy (float32 or float64, the
+    array's own precision).  An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample: the elements
+    at DUMP_MAX_ELEMS flat indices drawn without replacement by numpy's default_rng(DUMP_SEED), in increasing index
+    order — the same elements in every run and every build, so two dumps compare element for element.  Returns the
+    record's `outputs` entry."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        shape, total = list(t.shape), t.numel()
+        if total > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        out[name] = {"shape": shape, "dtype": str(a.dtype), "written": int(a.size),
+                     "sample": None if a.size == total else
+                     f"flat indices np.sort(default_rng({DUMP_SEED}).choice({total}, {DUMP_MAX_ELEMS}, replace=False))"}
+    return out
 
 
 def time_to_solution(conv, ms_step, eps=1e-6):
@@ -621,8 +674,8 @@ def base_record(args, value, ms_step, ws, warm, workload, mode, parallelism, rhs
         "warmup": args.warmup,
         "warmup_executed_steps": warm,
         "warmup_note": ("warmup = the requested --warmup; warmup_executed_steps = the untimed cycles actually run "
-                        "before the clock (>= warmup: whole calls of the timed vcycle(steps), so every HIP graph it "
-                        "replays is captured before timing)"),
+                        "before the clock (>= warmup: whole calls that replay the HIP graphs of the timed "
+                        "vcycle(steps), so every graph it replays is captured before timing)"),
         "ms_per_step": ms_step,
         "higher_is_better": True,
         "scaling": "strong" if (mode == "dd" and not args.weak) else "weak",
@@ -681,7 +734,7 @@ def run_dd(args, ws, rank, T, B, guard, emit):
                              batch=B, grid=grid, overlap_l0=ov, split_join=sj, **pkw)
                 s.set_rhs(**rhs)
                 s.load()
-                conv = contraction(s) if i == 0 else None
+                conv = contraction(s) if (i == 0 and args.full) else None
                 t, warm = time_steps(s, args.steps, args.warmup, ws)
                 captured = bool(s.comm.capturable and s._capture_ok and s.use_graph)
                 par = None
@@ -708,11 +761,6 @@ def run_dd(args, ws, rank, T, B, guard, emit):
              "dd_parity": par, "mode_seconds": round(time.perf_counter() - t0, 2)}
         results.append(r)
         if i == 0:
-            fine = time_fine_kernels(s.local, args.kernel_reps)
-            # the learned smoother joins no cycles: its dominant kernel is the slowest finest-level launch of the
-            # local cycle (timed in the rank's local V-cycle plan, which has the same finest-level launches)
-            dom = time_fine_launch_in_cycle(s.local) if args.smoother == "hjac" else None
-            roof, ns, fl = roofline_record(fine, s.local, args, dom=dom, ws=ws)
             p0, q0 = s.parts[0], s.cparts[0]
             workload = (f"{m + 1}x{nc + 1} {args.problem} {args.dtype} V-cycle, L={s.L}, V(1,1)"
                         f"{' (learned HRelax smoother)' if args.smoother == 'hjac' else ''}, domain-decomposed into "
@@ -723,12 +771,19 @@ def run_dd(args, ws, rank, T, B, guard, emit):
                            f"{s.depths}) once per V-cycle + all-gather of level {s.Ld}, redundant coarse solve")
             rec = base_record(args, r["value"], ms, ws, warm, workload, "dd", parallelism,
                               "ones" if args.problem == "interface" else "randn", s.L, B)
-            rec.update({"roofline": roof, "north_star_kernel": ns, "fine_level_kernels": fl,
-                        "vcycle_hbm_gbps_algorithmic": None, "vcycle_algorithmic_bytes": None,
-                        "residual_contraction_per_cycle": conv, "dd_modes": results, "cpu_baseline": None})
+            rec["dd_modes"] = results
+            if args.full:
+                fine = time_fine_kernels(s.local, args.kernel_reps)
+                # the learned smoother joins no cycles: its dominant kernel is the slowest finest-level launch of the
+                # local cycle (timed in the rank's local V-cycle plan, which has the same finest-level launches)
+                dom = time_fine_launch_in_cycle(s.local) if args.smoother == "hjac" else None
+                roof, ns, fl = roofline_record(fine, s.local, args, dom=dom, ws=ws)
+                rec.update({"roofline": roof, "north_star_kernel": ns, "fine_level_kernels": fl,
+                            "vcycle_hbm_gbps_algorithmic": None, "vcycle_algorithmic_bytes": None,
+                            "residual_contraction_per_cycle": conv, "cpu_baseline": None})
             if args.problem == "interface":
                 rec["config"]["transfer"] = ("learned ratio R/P/w" if "R" in pkw else "linear")
-            if ws > 1:
+            if ws > 1 and args.full:
                 # the same global grid on ONE GPU (rank 0; the others wait at the barrier): the strong-scaling base
                 # point of this line, so speed-up and efficiency follow from the line itself
                 del s
@@ -788,11 +843,18 @@ def run_single(args, ws, rank, T, B):
                 f"{', learned ratio R/P/w of FEANet/multigrid.py (BASELINE C3)' if learned else ''}), batch {B} per GPU")
     parallelism = "replicas (one independent problem per GPU)" if ws > 1 else "single GPU"
     s.load()
-    conv = contraction(s)
+    conv = contraction(s) if args.full else None  # ends with a load(): the timed cycles start from zero either way
     t, warm = time_steps(s, args.steps, args.warmup, ws)
     ms_step = t / args.steps * 1e3
     rec = base_record(args, dof / (t / args.steps), ms_step, ws, warm, workload, "single" if ws == 1 else "replicas",
                       parallelism, rhs, s.L, B)
+    if args.dump_outputs and rank == 0:  # before anything below touches the solver's buffers
+        rec["outputs"] = dump_outputs(args.dump_outputs, {"solution": s.solution()})
+    if args.problem == "interface":
+        rec["config"]["transfer"] = ("learned ratio R/P/w (feanet_amd/weights/multigrid_interface_ratio.npz)" if learned
+                                     else "linear (the reference's default RestrictionNet / ProlongationNet)")
+    if not args.full:
+        return rec
     fine = time_fine_kernels(s, args.kernel_reps)
     L0 = s.levels[0]
     metric_cfg = (L0.H == 4097 and L0.W == 4097 and B == 1 and args.dtype == "f64" and args.problem == "poisson")
@@ -813,9 +875,6 @@ def run_single(args, ws, rank, T, B):
         del s
         torch.cuda.empty_cache()
         rec["jacobi_same_grid"] = jacobi_same_grid(args, B, T, f)
-    if args.problem == "interface":
-        rec["config"]["transfer"] = ("learned ratio R/P/w (feanet_amd/weights/multigrid_interface_ratio.npz)" if learned
-                                     else "linear (the reference's default RestrictionNet / ProlongationNet)")
     if rank == 0 and ws == 1 and not args.no_cpu_baseline and args.problem == "poisson" and B == 1:
         log("[bench] timing the CPU oracle baseline ...")
         rec["cpu_baseline"] = cpu_baseline(n)
@@ -862,13 +921,23 @@ def main():
     ap.add_argument("--transfer", default="learned", choices=["learned", "linear"],
                     help="interface problem: the trained ratio R/P/w of FEANet/multigrid.py (BASELINE C3, default) or "
                          "the linear transfer operators")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure, each in runs of its own after the timed "
+                         "steps: the residual contraction and time to solution, the roofline of the dominant kernel and "
+                         "of every fine-level kernel, the CPU baseline, MG-Jacobi beside --smoother hjac and, on a "
+                         "decomposed run, the single-GPU base point.  Without it the run sets up, warms up, times "
+                         "--steps cycles and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the iterate the timed cycles ended on (what solution() returns) "
+                         "as DIR/solution.npy in the run's precision; a grid of more than 4 Mi nodes as a fixed seeded "
+                         "sample of 4 Mi of them (dump_outputs).  Single-GPU and replica runs (rank 0 writes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--no-dd-parity", action="store_true",
                     help="dd: skip the per-rank bitwise check against a global-grid single-GPU solver (it holds the "
                          "whole global grid on every rank: ~1 GB per 8193^2 fp64 field)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (gloo: multi-process rehearsal on one GPU, host-staged)")
-    ap.add_argument("--kernel-reps", type=int, default=50)
+    ap.add_argument("--kernel-reps", type=int, default=50, help="--full: launches per isolated kernel timing")
     ap.add_argument("--selftest-hang", type=float, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -894,6 +963,9 @@ def main():
 
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     mode = args.mode or ("dd" if ws > 1 else "single")
+    if args.dump_outputs and mode == "dd":
+        sys.exit("bench: --dump-outputs writes the single-GPU solver's iterate; a decomposed run (--mode dd) has no "
+                 "one array to write (its parity with the single-GPU solver is on the line: dd_parity)")
     ws, rank = dist_init(force=(mode == "dd"), backend=args.backend, timeout_s=args.dist_timeout)
     guard = PhaseGuard(rank)
     T = torch.float64 if args.dtype == "f64" else torch.float32

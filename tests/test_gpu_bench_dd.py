@@ -31,7 +31,7 @@ def test_bench_dd_line_parity(ranks, grid, extra):
     smoother (--problem interface --smoother hjac)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
-           "--gpus", str(ranks), "--steps", "3", "--warmup", "1", "--backend", "gloo", "--global-n", "1024",
+           "--gpus", str(ranks), "--full", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--global-n", "1024",
            "--kernel-reps", "2"] + (["--grid", grid] if grid else []) + extra
     env = dict(os.environ, OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -66,7 +66,7 @@ def test_bench_dd_line_parity(ranks, grid, extra):
 def test_bench_gpus_flag_launches_ranks():
     """`bench.py --gpus 2` with no launcher starts the two ranks itself (torch.distributed.run as a child
     process), forwards rank 0's one JSON line and records the decomposition mode it ran."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
            "--backend", "gloo", "--global-n", "1024", "--kernel-reps", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"

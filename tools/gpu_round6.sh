@@ -8,5 +8,5 @@ timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $T/smoke
 tail -1 $T/smoke.log
 bash tools/profile_round.sh $TAG || exit 1
 python3 tools/cycle_positions.py $T/trace > $T/cycle_positions.txt && cat $T/cycle_positions.txt
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $T/bench_steps20.json 2> $T/bench_steps20.err || { tail $T/bench_steps20.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $T/bench_steps20.json 2> $T/bench_steps20.err || { tail $T/bench_steps20.err; exit 1; }
 python3 -c "import json; d=json.load(open('$T/bench_steps20.json')); print('steps20', round(d['ms_per_step']*1e3, 2), 'us')"

@@ -16,7 +16,7 @@ for name in "$@"; do
   i=0
   for P in "${PASSES[@]}"; do
     i=$((i+1))
-    timeout -s KILL 150 rocprofv3 --pmc $P --output-format csv -d $T/${name}_p$i -o run -- python3 bench.py --no-cpu-baseline --kernel-reps 3 ${CFG[$name]} > $T/${name}_p$i.log 2>&1 || { echo "pmc $name pass $i failed"; tail -5 $T/${name}_p$i.log; exit 1; }
+    timeout -s KILL 150 rocprofv3 --pmc $P --output-format csv -d $T/${name}_p$i -o run -- python3 bench.py --full --no-cpu-baseline --kernel-reps 3 ${CFG[$name]} > $T/${name}_p$i.log 2>&1 || { echo "pmc $name pass $i failed"; tail -5 $T/${name}_p$i.log; exit 1; }
     echo "$name pass $i ok"
   done
   python3 tools/pmc_table.py $T/${name}_p*/*counter_collection.csv > $T/${name}_table.txt

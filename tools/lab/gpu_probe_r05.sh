@@ -18,12 +18,12 @@ for i in 1 2; do
     unset FEA_LAB_JREV; L=-
     [ $v = rev ] && export FEA_LAB_JREV=1
     [ $v = omz ] && L=tools/lab/lib_omz.so
-    timeout -k 10 200 python3 tools/lab/with_lib.py $L bench.py --no-cpu-baseline --kernel-reps 5 > $T/ab_${v}_$i.json 2> $T/ab_${v}_$i.err || { tail $T/ab_${v}_$i.err; exit 1; }
+    timeout -k 10 200 python3 tools/lab/with_lib.py $L bench.py --full --no-cpu-baseline --kernel-reps 5 > $T/ab_${v}_$i.json 2> $T/ab_${v}_$i.err || { tail $T/ab_${v}_$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$T/ab_${v}_$i.json')); print('$v run$i', round(d['ms_per_step']*1e3,2), 'us, join', round(d['roofline']['avg_launch_us'],2), 'sweep', round(d['north_star_kernel']['avg_launch_us'],2))"
   done
 done
 unset FEA_LAB_JREV
-P="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --kernel-reps 3"
+P="python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --kernel-reps 3"
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE -d $T/pmc1 -o pmc1 --output-format csv -- $P > $T/pmc1.log 2>&1 || { tail $T/pmc1.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY -d $T/pmc2 -o pmc2 --output-format csv -- $P > $T/pmc2.log 2>&1 || { tail $T/pmc2.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_SCA -d $T/pmc3 -o pmc3 --output-format csv -- $P > $T/pmc3.log 2>&1 || { tail $T/pmc3.log; exit 1; }

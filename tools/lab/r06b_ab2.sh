@@ -7,6 +7,6 @@ tail -2 $T/pytest.log
 BENCH_ARGS="--steps 1000" bash tools/lab/gpu_cfg_attrs.sh r06b_ab2/metric - TAIL_EXT=0 || exit 1
 BENCH_ARGS="--n 1024 --levels 6 --steps 1000" REPS="1 2" bash tools/lab/gpu_cfg_attrs.sh r06b_ab2/c2 - TAIL_EXT=0 || exit 1
 BENCH_ARGS="--n 1024 --dtype f32 --batch 256 --steps 40" REPS="1 2" bash tools/lab/gpu_cfg_attrs.sh r06b_ab2/c5 - TAIL_EXT=0 || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $T/trace -o run -- python3 bench.py --no-cpu-baseline --kernel-reps 5 --steps 1000 > $T/bench.json 2> $T/bench.err || { tail $T/bench.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $T/trace -o run -- python3 bench.py --full --no-cpu-baseline --kernel-reps 5 --steps 1000 > $T/bench.json 2> $T/bench.err || { tail $T/bench.err; exit 1; }
 python3 tools/trace_summary.py $T/trace > $T/trace.txt && head -12 $T/trace.txt
 python3 tools/cycle_positions.py $T/trace > $T/positions.txt 2>&1 && head -12 $T/positions.txt

@@ -9,5 +9,5 @@ for A in TAIL_F32_TABLES=1 TAIL_F32_TABLES=0; do
   echo "$A $(cat $T/hash.txt)"
 done
 BENCH_ARGS="--n 2048 --problem interface --steps 300" bash tools/lab/gpu_cfg_attrs.sh r06c_f32tab/c3 TAIL_F32_TABLES=1 TAIL_F32_TABLES=0 || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $T/trace_c3 -o run -- python3 bench.py --no-cpu-baseline --kernel-reps 5 --n 2048 --problem interface --steps 300 > $T/bench_c3.json 2> $T/bench_c3.err || { tail $T/bench_c3.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $T/trace_c3 -o run -- python3 bench.py --full --no-cpu-baseline --kernel-reps 5 --n 2048 --problem interface --steps 300 > $T/bench_c3.json 2> $T/bench_c3.err || { tail $T/bench_c3.err; exit 1; }
 python3 tools/cycle_positions.py $T/trace_c3 > $T/positions_c3.txt 2>&1 && cat $T/positions_c3.txt
