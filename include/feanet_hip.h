@@ -21,7 +21,7 @@
  *    values omega/d_p (d_p = ktab[p*9+4]); `pid` = uint8 pattern id per node (NULL:
  *    every node uses pattern 0).  ntab <= FEA_MAX_PATTERNS.
  *
- * Two families:
+ * Families ((3), the Krylov vector operations on the framed layout, is described where it starts):
  *  (1) "Generic" ops on contiguous NCHW tensors [B, C, H, W] — the drop-in operator
  *      boundary used by the FEANet.* shim modules (KNet/FNet/JacobiBlock/MultiGrid).
  *  (2) "mg" ops on FRAMED level buffers owned by the MultigridSolver: node (r, c)
@@ -551,6 +551,77 @@ int fea_dd_copy_rects(const void* rects, int nrects, int elem_size, void* stream
  * float32 geometry.  out[r * ld + c] = pattern id (0..15) of node (r, c), 0 on the boundary;
  * shape 0 = circle, 1 = square inclusion; size = plate edge length (the reference's `size`). */
 int fea_interface_pattern_map(uint8_t* out, long long ld, int N, int shape, double size, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * (3) Krylov vector operations of the multigrid-preconditioned conjugate gradient (feanet_amd.pcg.PCGSolver;
+ *     pcg_ops.hip).  No reference counterpart: the reference only iterates the V-cycle (FEANet/multigrid.py:159-185).
+ *     All fields are level-0 framed buffers (fea_mg_layout), B samples of H x W nodes.  r, p, z are zero on the
+ *     boundary nodes and the ghost ring; x carries the Dirichlet values on its boundary nodes.  K acts on interior
+ *     nodes only, with the tap order and table reads of the fea_mg_* kernels (pid / ktab / ntab as in section 2).
+ *     Every kernel also writes one partial sum per wave, in double, to part[b * fea_pcg_parts(H, W, elem) + i];
+ *     fea_pcg_scalar_step sums a sample's partials in index order (no atomics, the same order every launch and for
+ *     every batch size) and advances the sample's scalar block.  Nothing allocates or synchronises.
+ *
+ *     Scalar block: FEA_PCG_NSCALARS doubles per sample.  The caller sets EPS and RTOL before FEA_PCG_STEP_INIT
+ *     (RTOL < 0: the threshold is EPS, absolute; RTOL >= 0: RTOL * ||r0||); the steps own the rest.
+ * ------------------------------------------------------------------------- */
+#define FEA_PCG_NSCALARS 12
+#define FEA_PCG_RZ 0       /* r.z of the current iteration */
+#define FEA_PCG_RZ_PREV 1  /* r.z of the previous iteration */
+#define FEA_PCG_PAP 2      /* p.Kp */
+#define FEA_PCG_ALPHA 3    /* rz / pAp; 0 once the sample is frozen */
+#define FEA_PCG_BETA 4     /* rz / previous rz; 0 in the first iteration and once frozen */
+#define FEA_PCG_RNORM 5    /* ||r|| (recurrence residual) */
+#define FEA_PCG_DONE 6     /* 0 running, FEA_PCG_CONVERGED, FEA_PCG_BREAKDOWN */
+#define FEA_PCG_ITERS 7    /* iterations that moved x */
+#define FEA_PCG_EPS 8      /* in: absolute threshold */
+#define FEA_PCG_RTOL 9     /* in: relative threshold, < 0 for none */
+#define FEA_PCG_THRESH 10  /* the threshold in force */
+#define FEA_PCG_ROW 11     /* next history row */
+#define FEA_PCG_CONVERGED 1
+#define FEA_PCG_BREAKDOWN 2 /* pAp <= 0 or non-finite, r.z or ||r|| non-finite */
+/* steps of fea_pcg_scalar_step: which partial set was just written
+ *   INIT: r.r of fea_pcg_residual  -> ||r0||, threshold, done = (||r0|| <= threshold), history row 0
+ *   RZ:   r.z of fea_pcg_dot       -> rz, beta
+ *   PAP:  p.Kp of fea_pcg_direction -> alpha (a non-positive or non-finite pAp freezes the sample: breakdown)
+ *   RR:   r.r of fea_pcg_update    -> ||r||, iteration count, done, next history row
+ * A frozen sample has alpha = beta = 0: its x and r no longer move and its history rows repeat. */
+#define FEA_PCG_STEP_INIT 0
+#define FEA_PCG_STEP_RZ 1
+#define FEA_PCG_STEP_PAP 2
+#define FEA_PCG_STEP_RR 3
+
+/* partial sums per sample the kernels below write for an H x W grid (elem_size 4 or 8); -1 if unsupported */
+long long fea_pcg_parts(int H, int W, int elem_size);
+/* hist: [hist_rows, B] doubles, row FEA_PCG_ROW receives ||r|| (rows past hist_rows are dropped); B workgroups */
+int fea_pcg_scalar_step(const double* part, long long per, double* scalars, double* hist, int hist_rows, int B,
+                        int step, void* stream);
+/* r = f - K x on the interior, 0 on the boundary nodes; partials of r.r.  r may be f (not x). */
+int fea_pcg_residual_f32(const float* x, const float* f, float* r, const uint8_t* pid, const float* ktab, int ntab,
+                         double* part, int B, int H, int W, int ld, long long bstride, void* stream);
+int fea_pcg_residual_f64(const double* x, const double* f, double* r, const uint8_t* pid, const double* ktab, int ntab,
+                         double* part, int B, int H, int W, int ld, long long bstride, void* stream);
+/* p_out = z + beta p_in on the interior (beta = scalars[b][FEA_PCG_BETA], applied in T); partials of p_out.K p_out.
+ * Every strip rebuilds the new direction on its halo from z and p_in, so p_out must not be p_in (nor z): p ping-pongs. */
+int fea_pcg_direction_f32(const float* z, const float* p_in, float* p_out, const uint8_t* pid, const float* ktab,
+                          int ntab, const double* scalars, double* part, int B, int H, int W, int ld,
+                          long long bstride, void* stream);
+int fea_pcg_direction_f64(const double* z, const double* p_in, double* p_out, const uint8_t* pid, const double* ktab,
+                          int ntab, const double* scalars, double* part, int B, int H, int W, int ld,
+                          long long bstride, void* stream);
+/* x += alpha p, r -= alpha K p on the interior, in place (K p recomputed from p); partials of the new r.r.
+ * A sample whose FEA_PCG_DONE is set is left untouched (its r.r is summed again). */
+int fea_pcg_update_f32(const float* p, float* x, float* r, const uint8_t* pid, const float* ktab, int ntab,
+                       const double* scalars, double* part, int B, int H, int W, int ld, long long bstride,
+                       void* stream);
+int fea_pcg_update_f64(const double* p, double* x, double* r, const uint8_t* pid, const double* ktab, int ntab,
+                       const double* scalars, double* part, int B, int H, int W, int ld, long long bstride,
+                       void* stream);
+/* partials of r.z over the interior */
+int fea_pcg_dot_f32(const float* r, const float* z, double* part, int B, int H, int W, int ld, long long bstride,
+                    void* stream);
+int fea_pcg_dot_f64(const double* r, const double* z, double* part, int B, int H, int W, int ld, long long bstride,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 
   feanet_amd.ops          tensor-level HIP operators (KNet apply, Jacobi sweep, R, P, norms)
   feanet_amd.solver       MultigridSolver: fused-kernel V-cycle over framed level buffers
-  feanet_amd.mesh_setup   vectorised discretisation tables (pattern maps, stencils)
+  feanet_amd.pcg          PCGSolver: conjugate gradients preconditioned by that V-cycle
+  feanet_amd.mesh_setup  vectorised discretisation tables (pattern maps, stencils)
   FEANet.*                drop-in modules with the reference's names (sibling package)
 """
 from . import mesh_setup  # noqa: F401
@@ -13,7 +14,10 @@ def __getattr__(name):
     if name == "MultigridSolver":
         from .solver import MultigridSolver
         return MultigridSolver
-    if name in ("ops", "solver", "_lib"):
+    if name == "PCGSolver":
+        from .pcg import PCGSolver
+        return PCGSolver
+    if name in ("ops", "solver", "pcg", "_lib"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

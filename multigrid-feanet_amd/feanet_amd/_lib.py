@@ -66,6 +66,11 @@ _SIGS = {
     "mg_mid_up": [P, P, P, P, I, I, I, I, P, P, I, P, I, "S", I, I, P],
     "mg_hmid_down": [P, P, P, I, I, I, P, P, I, P, I, P, I, "S", I, P],
     "mg_hmid_up": [P, P, P, P, P, I, I, I, P, P, I, P, I, P, I, "S", I, P],
+    # Krylov vector operations (feanet_amd.pcg): (..., B, H, W, ld, bstride, stream)
+    "pcg_residual": [P, P, P, P, P, I, P, I, I, I, I, LL, P],
+    "pcg_direction": [P, P, P, P, P, I, P, P, I, I, I, I, LL, P],
+    "pcg_update": [P, P, P, P, P, I, P, P, I, I, I, I, LL, P],
+    "pcg_dot": [P, P, P, I, I, I, I, LL, P],
 }
 _EXTRA = {
     "fea_abi_version": ([], I),
@@ -80,6 +85,8 @@ _EXTRA = {
     "fea_interface_pattern_map": ([P, LL, I, I, F64, P], I),
     "fea_dd_copy_blocks": ([P, I, I, I, P], I),
     "fea_dd_copy_rects": ([P, I, I, P], I),
+    "fea_pcg_parts": ([I, I, I], LL),
+    "fea_pcg_scalar_step": ([P, LL, P, P, I, I, I, P], I),
     "fea_stencil_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),
     "fea_stencil_weight_grad_ws_bytes_f64": ([I, I, I, I], ctypes.c_size_t),
     "fea_transfer_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),

@@ -1,0 +1,253 @@
+"""PCGSolver: conjugate gradients preconditioned by one V-cycle, resident on one MI355X.
+
+The stationary iteration of MultigridSolver needs the V-cycle's error propagator to contract; with rediscretised
+coarse operators and two Jacobi sweeps as the coarse solve it stops doing so once the two-material contrast leaves
+the reference's prop=(1, 20).  The same V(nu, nu) cycle from a zero guess is a symmetric positive definite operator
+M (symmetric smoother, R = P^T, positive semi-definite coarse term), so it can precondition CG, which converges
+whatever the contraction number of the stationary iteration.
+
+One iteration (all on the device, nothing read by the host):
+
+    z = M r                      MultigridSolver(zero_start=True): its right-hand side buffer IS r, its end iterate IS z
+    rz = r.z                     fea_pcg_dot        + fea_pcg_scalar_step(RZ):  beta = rz / rz_prev
+    p' = z + beta p              fea_pcg_direction  + fea_pcg_scalar_step(PAP): alpha = rz / p'.Kp'
+    x += alpha p', r -= alpha Kp'  fea_pcg_update   + fea_pcg_scalar_step(RR):  ||r||, done flag, history row
+
+p ping-pongs between two buffers (the direction kernel rebuilds p' on its halos from z and p).  A sample freezes
+(alpha = beta = 0, x and r stop moving, history rows repeat) once ||r|| <= its threshold or on a breakdown
+(pAp <= 0 or non-finite, r.z non-finite), so its result depends neither on the other samples nor on how often the
+host looks at the flags.  Blocks of iterations are replayed as HIP graphs.
+"""
+import numpy as np
+import torch
+
+from . import _lib, mesh_setup as ms, ops
+from .solver import MultigridSolver
+
+# scalar block layout and steps: include/feanet_hip.h (FEA_PCG_*)
+NSCALARS = 12
+RZ, RZ_PREV, PAP, ALPHA, BETA, RNORM, DONE, ITERS, EPS, RTOL, THRESH, ROW = range(NSCALARS)
+CONVERGED, BREAKDOWN = 1, 2
+STEP_INIT, STEP_RZ, STEP_PAP, STEP_RR = range(4)
+
+
+class PCGSolver:
+    """Multigrid-preconditioned conjugate gradients for MultigridSolver's problems (one GPU).
+
+    Args as MultigridSolver (n, levels, problem, dtype, batch, omega, size, prop, shape, rows, R, P, w), and
+        nu: pre- and post-sweeps of the preconditioning V(nu, nu) cycle (equal, so the cycle is symmetric).
+        graph: replay blocks of iterations as HIP graphs.
+        check_every: solve() reads the samples' done flags every this many iterations, and at no other time.
+
+    Rejected with ValueError, because the preconditioner would not be symmetric: compat schedules, the learned
+    smoother, and R / P tables that are not one kernel repeated with R == P (per-pattern learned tables pick the
+    kernel by fine-node pattern in R and coarse-node pattern in P, so P != R^T).  The ratios w may be any positive
+    pair.
+    """
+
+    GRAPH_ITERS = 8    # iterations per captured HIP graph
+    HIST_ROWS = 1024   # history rows kept on the device (grown by solve(max_iters=...))
+
+    def __init__(self, n, levels=None, problem="poisson", dtype=torch.float64, device=None, batch=1,
+                 omega=2.0 / 3.0, size=2.0, prop=(1, 20), shape=0, rows=None, R=None, P=None, w=(1.0, 1.0), nu=1,
+                 graph=True, check_every=8, smoother="jac", compat=None):
+        if compat is not None:
+            raise ValueError("PCGSolver: compat schedules are not symmetric V-cycles")
+        if smoother != "jac":
+            raise ValueError(f"PCGSolver: smoother={smoother!r} is not symmetric; only 'jac' can precondition CG")
+        if int(nu) < 1:
+            raise ValueError("PCGSolver: nu >= 1 (without smoothing the V-cycle is only semi-definite)")
+        if int(check_every) < 1:
+            raise ValueError("PCGSolver: check_every >= 1")
+        lin = ms.linear_transfer_kernel() / np.float32(4.0)
+        tabs = [lin[None] if t is None else np.asarray(torch.as_tensor(t).detach().cpu().float().numpy(), np.float32)
+                for t in (R, P)]
+        Rk, Pk = (t.reshape(-1, 3, 3) for t in tabs)
+        if not ((Rk == Rk[:1]).all() and (Pk == Pk[:1]).all() and np.array_equal(Rk[0], Pk[0])):
+            raise ValueError("PCGSolver: R and P must be one 3x3 kernel, the same for both (P = R^T); per-pattern "
+                             "tables make the V-cycle non-symmetric")
+        wl = [float(v) for v in (w.detach().cpu().tolist() if torch.is_tensor(w) else w)]
+        if not (wl[0] > 0 and wl[1] > 0):
+            raise ValueError("PCGSolver: the ratios w must be positive")
+        self.mg = MultigridSolver(n, levels=levels, problem=problem, dtype=dtype, device=device, batch=batch,
+                                  omega=omega, size=size, prop=prop, shape=shape, R=R, P=P, w=w, nu1=int(nu),
+                                  nu2=int(nu), graph=False, rows=rows, zero_start=True, smoother="jac")
+        mg = self.mg
+        self.device, self.dtype, self.B = mg.device, mg.dtype, mg.B
+        self.use_graph = bool(graph)
+        self.check_every = int(check_every)
+        L0 = mg.levels[0]
+        self.r = L0.f  # the preconditioner's right-hand side buffer is the residual
+        self.x, self.b, p0, p1 = (torch.zeros_like(L0.a) for _ in range(4))
+        self.p = (p0, p1)
+        self._parity = 0  # the next iteration reads p[_parity] and writes p[1 - _parity]
+        self._zname = None
+        self.per = int(_lib.lib().fea_pcg_parts(L0.H, L0.W, 4 if dtype == torch.float32 else 8))
+        self.part = torch.zeros(self.B * self.per, dtype=torch.float64, device=self.device)
+        self.sc = torch.zeros((self.B, NSCALARS), dtype=torch.float64, device=self.device)
+        self.hist = torch.zeros((self.HIST_ROWS, self.B), dtype=torch.float64, device=self.device)
+        self._graphs = {}
+        self._eager_runs = {}
+        self._loaded = False
+        self.flags = None        # after solve(): per-sample 1 converged, 2 breakdown, 0 still running
+        self.iterations = None   # after solve(): per-sample iterations that moved x
+
+    # ------------------------------------------------------------------ problem data
+    @property
+    def H(self):
+        return self.mg.H
+
+    @property
+    def W(self):
+        return self.mg.W
+
+    def set_rhs(self, f=None, F=None):
+        """The assembled right-hand side f, or the nodal source F (FNet applied on the device)."""
+        if (f is None) == (F is None):
+            raise ValueError("PCGSolver.set_rhs: give exactly one of f (assembled) or F (source)")
+        mg = self.mg
+        if F is not None:
+            f = ops.conv3x3(mg._check_field(F, "F"), torch.from_numpy(mg.mass))
+        mg._pack(mg._check_field(f, "f"), self.b, reset=False)
+        self._loaded = False
+
+    def set_boundary(self, bc_value=None, geometry_idx=None):
+        """Dirichlet data of the fine level (square geometry only, as MultigridSolver); used by the next load()."""
+        self.mg.set_boundary(bc_value, geometry_idx)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _kargs(self):
+        mg, L0 = self.mg, self.mg.levels[0]
+        return (None if L0.pid is None else L0.pid.data_ptr(), mg.ktab.data_ptr(), mg.ntab)
+
+    def _scalar(self, step):
+        return ("pcg_scalar_step", (self.part.data_ptr(), self.per, self.sc.data_ptr(), self.hist.data_ptr(),
+                                    self.hist.shape[0], self.B, step))
+
+    def _launch(self, launches):
+        stream = self._stream()
+        for name, args in launches:
+            if name == "pcg_scalar_step":
+                _lib.call_raw(name, *args, stream)
+            else:
+                _lib.call(name, self.dtype, *args, stream)
+
+    def load(self, u0=None, eps=0.0, rtol=None):
+        """Start from u0 (reset_boundary applied: u*geo + bc): r = b - K x, history row 0 = ||r0||.  Samples stop at
+        ||r|| <= rtol * ||r0|| if rtol is given, else at ||r|| <= eps."""
+        mg, L0 = self.mg, self.mg.levels[0]
+        if u0 is not None:
+            u0 = mg._check_field(u0, "u0")
+        mg._pack(u0, self.x, bc=getattr(mg, "_bc", None))
+        self.p[0].zero_()
+        self.p[1].zero_()
+        self.sc.zero_()
+        self.sc[:, EPS] = float(eps)
+        self.sc[:, RTOL] = -1.0 if rtol is None else float(rtol)
+        self._parity = 0
+        self._launch([("pcg_residual", (self.x.data_ptr(), self.b.data_ptr(), self.r.data_ptr()) + self._kargs() +
+                       (self.part.data_ptr(),) + L0.geom()), self._scalar(STEP_INIT)])
+        self._loaded = True
+
+    # ------------------------------------------------------------------ iteration
+    def _iteration(self, q):
+        """Launches of one iteration reading p[q], writing p[1 - q]."""
+        mg, L0 = self.mg, self.mg.levels[0]
+        plan, end = mg._plan("a")  # from a zero guess: the plan does not depend on the start buffer
+        if self._zname is None:
+            self._zname = end
+        assert end == self._zname and L0.buf(end).data_ptr() != self.r.data_ptr(), "the preconditioner's output moved"
+        z = L0.buf(end).data_ptr()
+        g, ka, part, sc = L0.geom(), self._kargs(), self.part.data_ptr(), self.sc.data_ptr()
+        pin, pout = self.p[q].data_ptr(), self.p[1 - q].data_ptr()
+        return list(plan) + [
+            ("pcg_dot", (self.r.data_ptr(), z, part) + g), self._scalar(STEP_RZ),
+            ("pcg_direction", (z, pin, pout) + ka + (sc, part) + g), self._scalar(STEP_PAP),
+            ("pcg_update", (pout, self.x.data_ptr(), self.r.data_ptr()) + ka + (sc, part) + g),
+            self._scalar(STEP_RR)]
+
+    def krylov_launches_per_iteration(self):
+        return 6
+
+    def _run_block(self, q, nb):
+        key = (q, nb, self.hist.data_ptr())
+        if not self.use_graph or self._eager_runs.get(key, 0) == 0:
+            self._eager_runs[key] = 1
+            for i in range(nb):
+                self._launch(self._iteration((q + i) % 2))
+            return
+        g = self._graphs.get(key)
+        if g is None:
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.graph(g, stream=s):
+                for i in range(nb):
+                    self._launch(self._iteration((q + i) % 2))
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            self._graphs[key] = g
+        g.replay()
+
+    def iterate(self, k=1):
+        """k iterations on the resident state (asynchronous; no host sync)."""
+        if not self._loaded:
+            raise RuntimeError("PCGSolver.iterate: call load() (after set_rhs) first")
+        while k > 0:
+            nb = min(k, self.GRAPH_ITERS)
+            self._run_block(self._parity, nb)
+            self._parity = (self._parity + nb) % 2
+            k -= nb
+
+    def solution(self):
+        """Current iterate as a contiguous [B, 1, H, W] tensor."""
+        L0 = self.mg.levels[0]
+        out = torch.empty((self.B, 1, self.H, self.W), dtype=self.dtype, device=self.device)
+        _lib.call("mg_unpack", self.dtype, self.x.data_ptr(), out.data_ptr(), *L0.geom(), self._stream())
+        return out
+
+    def residual_norm(self):
+        """Per-sample true residual ||(b - K x)[1:-1, 1:-1]||_2 (float64 device tensor [B]), recomputed from x."""
+        mg, L0 = self.mg, self.mg.levels[0]
+        _lib.call("mg_residual_norm", self.dtype, self.x.data_ptr(), self.b.data_ptr(), *self._kargs(),
+                  mg.norm_out.data_ptr(), mg.ws.data_ptr(), *L0.geom(), 0, 0, 0, 0, self._stream())
+        return mg.norm_out.clone()
+
+    def scalars(self):
+        """The per-sample scalar blocks ([B, 12] float64, host copy; synchronises)."""
+        return self.sc.cpu().numpy()
+
+    def history(self):
+        """Recurrence residual norms so far: list of per-sample arrays, entry 0 the initial residual, up to the
+        last iteration that moved any sample (synchronises)."""
+        sc = self.scalars()
+        rows = min(int(sc[:, ITERS].max()) + 1, self.hist.shape[0])
+        h = self.hist[:rows].cpu().numpy()
+        return [h[i].copy() for i in range(rows)]
+
+    def solve(self, u0=None, f=None, F=None, eps=1e-6, rtol=None, max_iters=100, bc_value=None):
+        """Iterate until every sample is frozen (converged: ||r_b|| <= eps, or <= rtol * ||r0_b|| if rtol is given;
+        or broken down) or max_iters.  Returns (u [B, 1, H, W], history as MultigridSolver.solve: a list of
+        per-sample arrays, first entry the initial residual).  self.flags / self.iterations hold the per-sample
+        outcome.  The host reads the done flags every check_every iterations and at no other time."""
+        if bc_value is not None:
+            self.set_boundary(bc_value)
+        if f is not None or F is not None:
+            self.set_rhs(f=f, F=F)
+        if max_iters + 1 > self.hist.shape[0]:
+            self.hist = torch.zeros((max_iters + 1, self.B), dtype=torch.float64, device=self.device)
+            self._graphs.clear()
+            self._eager_runs.clear()
+        self.load(u0, eps=eps, rtol=rtol)
+        it = 0
+        while it < max_iters:
+            k = min(self.check_every, max_iters - it)
+            self.iterate(k)
+            it += k
+            if bool((self.sc[:, DONE] != 0).all().item()):
+                break
+        sc = self.scalars()
+        self.flags = sc[:, DONE].astype(np.int64)
+        self.iterations = sc[:, ITERS].astype(np.int64)
+        return self.solution(), self.history()
