@@ -623,6 +623,34 @@ int fea_pcg_dot_f32(const float* r, const float* z, double* part, int B, int H, 
 int fea_pcg_dot_f64(const double* r, const double* z, double* part, int B, int H, int W, int ld, long long bstride,
                     void* stream);
 
+/* Mixed precision (feanet_amd.pcg.PCGSolver(dtype=float64, precond_dtype=float32)): the Krylov fields x, r, p stay
+ * fp64 framed buffers (ld, bstride: fea_mg_layout(H, W, 8)); the preconditioner is an fp32 hierarchy, whose level-0
+ * right-hand side r32 and end iterate z32 are fp32 framed buffers of the same H x W nodes (ld32, bstride32:
+ * fea_mg_layout(H, W, 4); ld32 a multiple of 32, ld of 16).  The kernels run on the fp64 task grid — partials are
+ * those of the fp64 geometry, fea_pcg_parts(H, W, 8), in the same slot order — and reach the fp32 field through its
+ * own frame offset (31 elements) and pitch.  pid and ktab are the fp64 frame's pattern map and an fp64 table.
+ *
+ * Every narrowing stores float(r * sb[b]): sb[b] is the power of two that puts ||r0|| * sb[b] in [1, 2), fixed for
+ * the solve (1 if ||r0|| is 0 or not finite), so the fp32 cycle neither underflows after many decades of reduction
+ * nor depends on the units of the right-hand side; CG is invariant to a constant scale of the preconditioner's
+ * input (z32, r.z and alpha carry the factor).  Only interior nodes of r32 are written: its boundary nodes, ghost
+ * rows and pad columns stay as they are (zero).  No fp64 field may share memory with an fp32 one. */
+/* r32 = float(r * sb[b]) on the interior; sb[b] is derived from scalars[b][FEA_PCG_RNORM] and stored (sb: [B]
+ * doubles).  Once per solve, after FEA_PCG_STEP_INIT. */
+int fea_pcg_narrow_f64f32(const double* r, float* r32, const double* scalars, double* sb, int B, int H, int W, int ld,
+                          long long bstride, int ld32, long long bstride32, void* stream);
+/* partials of r.z32 (z32 widened, products and sums in double) */
+int fea_pcg_dot_f64f32(const double* r, const float* z32, double* part, int B, int H, int W, int ld,
+                       long long bstride, int ld32, long long bstride32, void* stream);
+/* p_out = z32 + beta p_in in double (z32 widened; halos rebuilt with the same expression); partials of p_out.K p_out */
+int fea_pcg_direction_f64f32(const float* z32, const double* p_in, double* p_out, const uint8_t* pid,
+                             const double* ktab, int ntab, const double* scalars, double* part, int B, int H, int W,
+                             int ld, long long bstride, int ld32, long long bstride32, void* stream);
+/* fea_pcg_update_f64, and r32 = float(r_new * sb[b]) on the interior.  A frozen sample leaves x, r and r32 untouched. */
+int fea_pcg_update_f64f32(const double* p, double* x, double* r, float* r32, const uint8_t* pid, const double* ktab,
+                          int ntab, const double* scalars, const double* sb, double* part, int B, int H, int W, int ld,
+                          long long bstride, int ld32, long long bstride32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,16 @@
 // part[(b * ntr + t) * nstrips + s]; the task height is chosen as for one sample, so a sample's partial set — and
 // with it every reduced scalar — is the same bits whatever the batch it runs in.  No atomics, nothing allocates or
 // synchronises, safe under stream capture.
+//
+// Mixed precision (fea_pcg_*_f64f32): the Krylov state stays in fp64, the preconditioner runs on an fp32 framed
+// hierarchy.  The same fp64 task grid addresses the fp32 level-0 field through Frame<float>::OFF and its own ld / bs
+// (column 1 of both frames is 128-byte aligned; a lane's two columns are one aligned 8-byte access there):
+//   narrow     r32 = float(r s_b)                  (interior; s_b from the sample's ||r0||)    12 B / node
+//   dot        partials of r.widen(z32)                                                        12 B
+//   direction  p_out = widen(z32) + beta p_in      (window rows of z32 loaded in fp32, widened) 20 B
+//   update     as above, also r32 = float(r_new s_b)                                           44 B
+// s_b is one power of two per sample, fixed for the solve (sb[b], written by the narrowing of load()), so products
+// with it are exact and CG does not see it.  Only interior nodes of r32 are ever written.
 #include "framed_strip.h"
 
 namespace fea {
@@ -37,12 +47,23 @@ struct PcgArgs {
   int H, W, ld;
   long long bs;
   int nstrips, ntr, rb;
+  // mixed precision (T = double): the fp32 level-0 field of the preconditioner in its own frame
+  const float* z32;  // direction, dot: the preconditioner's end iterate
+  float* r32;        // narrow, update: the preconditioner's right-hand side
+  const double* sb;  // update: per-sample scale s_b (narrow: written through sbw)
+  double* sbw;
+  int ld32;
+  long long bs32;
 };
 
-template <typename T, bool MULTI, int MODE, bool NT>
+// MIX: the f64f32 form — the direction's z, the update's second residual store live in the fp32 frame
+template <typename T, bool MULTI, int MODE, bool NT, bool MIX = false>
 __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
   using F = Frame<T>;
   constexpr int V = F::VEC;
+  static_assert(!MIX || (std::is_same<T, double>::value && MODE != kPcgResidual), "f64f32: direction and update");
+  constexpr bool kMixDir = MIX && MODE == kPcgDirection;
+  using ZT = typename std::conditional<kMixDir, float, T>::type;  // element type of the field z is read from
   __shared__ T tab[MULTI ? FEA_MAX_PATTERNS * kTabStride : 1];
   if constexpr (MULTI) {
     load_tables<T>(tab, g.ktab, nullptr, g.ntab, nullptr, nullptr, 0);
@@ -63,8 +84,12 @@ __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
   }
   const long long poff = F::OFF + c0;
   const long long boff = (long long)id.b * g.bs + poff;
-  const T* __restrict__ va = g.v + boff;
+  const T* __restrict__ va = kMixDir ? nullptr : g.v + boff;
   const T* __restrict__ vb = MODE == kPcgDirection ? g.v2 + boff : nullptr;
+  // the strip's first column in the fp32 frame, and that frame's row offsets
+  const long long boff32 = MIX ? (long long)id.b * g.bs32 + Frame<float>::OFF + c0 : 0;
+  const int ld32 = MIX ? g.ld32 : 0;
+  auto rowo32 = [&](int r) -> long long { return (long long)(min(r, H) + 1) * ld32; };
   const uint8_t* __restrict__ pb = MULTI ? g.pid + poff : nullptr;
   const int ld = g.ld;
   auto rowo = [&](int r) -> long long { return (long long)(min(r, H) + 1) * ld; };
@@ -73,11 +98,13 @@ __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
   T coef = T(0);  // beta (direction) / alpha (update): formed in double, applied in T
   if constexpr (MODE == kPcgDirection) coef = (T)sc[FEA_PCG_BETA];
   if constexpr (MODE == kPcgUpdate) coef = (T)sc[FEA_PCG_ALPHA];
+  double sbv = 1.0;
+  if constexpr (MIX && MODE == kPcgUpdate) sbv = g.sb[id.b];
   double s = 0.0;
 
   if constexpr (MODE == kPcgUpdate) {
-    // a frozen sample (alpha = 0): x and r stay as they are, whatever p holds; its r.r is summed again in the
-    // same order, so the history row repeats bit for bit
+    // a frozen sample (alpha = 0): x and r (and r32) stay as they are, whatever p holds; its r.r is summed again in
+    // the same order, so the history row repeats bit for bit
     if (sc[FEA_PCG_DONE] != 0.0) {
       const T* rb_ = g.r + boff;
       for (int r = r0; r < r1; ++r) {
@@ -107,17 +134,27 @@ __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
   }
 
   // a window row of the field K acts on; the direction's is z + beta p_in on every window column
+  // (f64f32: z's window row is loaded and shifted in fp32 — the same lanes' columns, half the bytes — then widened)
   struct RawV {
-    RawRow<T, V> a, b;
+    RawRow<ZT, V> a;
+    RawRow<T, V> b;
   };
   auto raw_v = [&](int r) {
     RawV w;
-    w.a = raw_row<T, V>(va + rowo(r), lane);
+    if constexpr (kMixDir) w.a = raw_row<float, V>(g.z32 + boff32 + rowo32(r), lane);
+    else w.a = raw_row<T, V>(va + rowo(r), lane);
     if constexpr (MODE == kPcgDirection) w.b = raw_row<T, V>(vb + rowo(r), lane);
     return w;
   };
   auto fin_v = [&](const RawV& w) {
-    Row<T, V> a = finish(w.a);
+    Row<T, V> a;
+    if constexpr (kMixDir) {
+      const Row<float, V> z = finish(w.a);
+#pragma unroll
+      for (int j = 0; j < V + 3; ++j) a.a[j] = (T)z.a[j];
+    } else {
+      a = finish(w.a);
+    }
     if constexpr (MODE == kPcgDirection) {
       const Row<T, V> b = finish(w.b);
 #pragma unroll
@@ -168,6 +205,12 @@ __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
     if constexpr (MODE == kPcgUpdate) {
       store_masked<T, V, NT>(g.r + ro, o, cl, W);
       store_masked<T, V, NT>(g.x + ro, xv, cl, W);
+      if constexpr (MIX) {
+        float nv[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) nv[k] = (float)(o[k] * sbv);
+        store_masked<float, V, NT>(g.r32 + boff32 + rowo32(r) + V * lane, nv, cl, W);
+      }
     } else {
       store_masked<T, V, NT>(g.out + ro, o, cl, W);
     }
@@ -184,11 +227,12 @@ __global__ __launch_bounds__(256) void k_pcg(PcgArgs<T> g) {
   if (lane == 0) g.part[pslot] = s;
 }
 
-// partials of r.z over the interior (pointwise: no window)
-template <typename T>
+// partials of r.z over the interior (pointwise: no window); Z = float: z in the fp32 frame (f64f32)
+template <typename T, typename Z = T>
 __global__ __launch_bounds__(256) void k_pcg_dot(PcgArgs<T> g) {
   using F = Frame<T>;
   constexpr int V = F::VEC;
+  constexpr bool MIX = !std::is_same<Z, T>::value;
   const TaskId id = decode_task(g.nstrips, g.ntr);
   if (!id.valid) return;
   const int lane = lane_id();
@@ -198,19 +242,59 @@ __global__ __launch_bounds__(256) void k_pcg_dot(PcgArgs<T> g) {
   const int cl = 1 + id.s * F::SW + V * lane;
   const long long boff = (long long)id.b * g.bs + F::OFF + cl;
   const T* __restrict__ a = g.v + boff;
-  const T* __restrict__ b = g.v2 + boff;
+  const Z* __restrict__ b;
+  if constexpr (MIX) b = g.z32 + (long long)id.b * g.bs32 + Frame<Z>::OFF + cl;
+  else b = g.v2 + boff;
+  const int ldz = MIX ? g.ld32 : g.ld;
   double s = 0.0;
   for (int r = r0; r < r1; ++r) {
     const long long ro = (long long)(r + 1) * g.ld;
-    T av[V], bv[V];
+    T av[V];
+    Z bv[V];
     vload<T, V>(a + ro, av);
-    vload<T, V>(b + ro, bv);
+    vload<Z, V>(b + (long long)(r + 1) * ldz, bv);
 #pragma unroll
     for (int k = 0; k < V; ++k)
       if (cl + k <= W - 2) s += (double)av[k] * (double)bv[k];
   }
   s = wave_sum(s);
   if (lane == 0) g.part[((long long)id.b * g.ntr + id.t) * g.nstrips + id.s] = s;
+}
+
+// The per-sample scale of the f64f32 path: the power of two that puts ||r0|| s_b in [1, 2); 1 for ||r0|| = 0 or not
+// finite.  Formed from the exponent field (subnormal ||r0||: 2^1023; ||r0|| >= 2^1023: 2^-1022, so s_b is a normal
+// number), the same bits in every wave.
+__device__ __forceinline__ double pcg_scale(double rn) {
+  const long long ex = (__double_as_longlong(rn) >> 52) & 0x7ff;
+  if (!(rn > 0.0) || ex == 0x7ff) return 1.0;
+  const long long e = 2046 - ex;
+  return __longlong_as_double((e < 1 ? 1ll : e) << 52);
+}
+
+// r32 = float(r s_b) on the interior (pointwise), s_b from the sample's FEA_PCG_RNORM; the sample's first task stores it
+template <bool NT>
+__global__ __launch_bounds__(256) void k_pcg_narrow(PcgArgs<double> g) {
+  using F = Frame<double>;
+  constexpr int V = F::VEC;
+  const TaskId id = decode_task(g.nstrips, g.ntr);
+  if (!id.valid) return;
+  const int lane = lane_id();
+  const int H = g.H, W = g.W;
+  const int r0 = 1 + id.t * g.rb;
+  const int r1 = min(r0 + g.rb, H - 1);
+  const int cl = 1 + id.s * F::SW + V * lane;
+  const double sbv = pcg_scale(g.sc[(long long)id.b * FEA_PCG_NSCALARS + FEA_PCG_RNORM]);
+  if (id.s == 0 && id.t == 0 && lane == 0) g.sbw[id.b] = sbv;
+  const double* __restrict__ a = g.v + (long long)id.b * g.bs + F::OFF + cl;
+  float* __restrict__ o = g.r32 + (long long)id.b * g.bs32 + Frame<float>::OFF + cl;
+  for (int r = r0; r < r1; ++r) {
+    double av[V];
+    float nv[V];
+    vload<double, V>(a + (long long)(r + 1) * g.ld, av);
+#pragma unroll
+    for (int k = 0; k < V; ++k) nv[k] = (float)(av[k] * sbv);
+    store_masked<float, V, NT>(o + (long long)(r + 1) * g.ld32, nv, cl, W);
+  }
 }
 
 // One workgroup per sample: the sample's `per` partials summed in index order (the scheme of k_norm_final), then
@@ -321,17 +405,17 @@ extern "C" int fea_pcg_scalar_step(const double* part, long long per, double* sc
   FEA_LAUNCH_CHECK();
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool MIX = false>
 static void pcg_launch(const PcgArgs<T>& g, int B, void* stream) {
   const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
   hipStream_t s = (hipStream_t)stream;
   const bool nt = pcg_nt<T>(B, g.bs);
   if (g.ntab > 1) {
-    if (nt) k_pcg<T, true, MODE, true><<<grid, 256, 0, s>>>(g);
-    else k_pcg<T, true, MODE, false><<<grid, 256, 0, s>>>(g);
+    if (nt) k_pcg<T, true, MODE, true, MIX><<<grid, 256, 0, s>>>(g);
+    else k_pcg<T, true, MODE, false, MIX><<<grid, 256, 0, s>>>(g);
   } else {
-    if (nt) k_pcg<T, false, MODE, true><<<grid, 256, 0, s>>>(g);
-    else k_pcg<T, false, MODE, false><<<grid, 256, 0, s>>>(g);
+    if (nt) k_pcg<T, false, MODE, true, MIX><<<grid, 256, 0, s>>>(g);
+    else k_pcg<T, false, MODE, false, MIX><<<grid, 256, 0, s>>>(g);
   }
 }
 
@@ -380,3 +464,67 @@ static void pcg_launch(const PcgArgs<T>& g, int B, void* stream) {
 
 FEA_PCG_API(f32, float)
 FEA_PCG_API(f64, double)
+
+// ---------------------------------------------------------------------------
+// f64f32: fp64 Krylov fields (ld, bs) next to the preconditioner's fp32 level-0 field (ld32, bs32)
+// ---------------------------------------------------------------------------
+static inline bool pcg_mix_ok(int B, int H, int W, int ld, long long bs, int ld32, long long bs32) {
+  return B > 0 && layout_ok<double>(H, W, ld, bs) && layout_ok<float>(H, W, ld32, bs32);
+}
+
+static PcgArgs<double> pcg_mix_args(int H, int W, int ld, long long bs, int ld32, long long bs32) {
+  PcgArgs<double> g = pcg_args<double>(H, W, ld, bs);
+  g.ld32 = ld32;
+  g.bs32 = bs32;
+  return g;
+}
+
+extern "C" int fea_pcg_narrow_f64f32(const double* r, float* r32, const double* scalars, double* sb, int B, int H,
+                                     int W, int ld, long long bs, int ld32, long long bs32, void* stream) {
+  if (!r || !r32 || !scalars || !sb || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32) || (const void*)r32 == (const void*)r ||
+      sb == scalars)
+    return FEA_EINVAL;
+  PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
+  g.v = r; g.r32 = r32; g.sc = scalars; g.sbw = sb;
+  const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
+  if (pcg_nt<double>(B, bs)) k_pcg_narrow<true><<<grid, 256, 0, (hipStream_t)stream>>>(g);
+  else k_pcg_narrow<false><<<grid, 256, 0, (hipStream_t)stream>>>(g);
+  FEA_LAUNCH_CHECK();
+}
+
+extern "C" int fea_pcg_dot_f64f32(const double* r, const float* z32, double* part, int B, int H, int W, int ld,
+                                  long long bs, int ld32, long long bs32, void* stream) {
+  if (!r || !z32 || !part || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32)) return FEA_EINVAL;
+  PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
+  g.v = r; g.z32 = z32; g.part = part;
+  k_pcg_dot<double, float><<<mg_grid(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(g);
+  FEA_LAUNCH_CHECK();
+}
+
+extern "C" int fea_pcg_direction_f64f32(const float* z32, const double* p_in, double* p_out, const uint8_t* pid,
+                                        const double* ktab, int ntab, const double* scalars, double* part, int B,
+                                        int H, int W, int ld, long long bs, int ld32, long long bs32, void* stream) {
+  if (!z32 || !p_in || !p_out || !scalars || !part || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32) ||
+      !pcg_tab_ok(ktab, ntab, pid) || p_out == p_in || (const void*)p_out == (const void*)z32)
+    return FEA_EINVAL;
+  PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
+  g.z32 = z32; g.v2 = p_in; g.out = p_out; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars;
+  g.part = part;
+  pcg_launch<double, kPcgDirection, true>(g, B, stream);
+  FEA_LAUNCH_CHECK();
+}
+
+extern "C" int fea_pcg_update_f64f32(const double* p, double* x, double* r, float* r32, const uint8_t* pid,
+                                     const double* ktab, int ntab, const double* scalars, const double* sb,
+                                     double* part, int B, int H, int W, int ld, long long bs, int ld32,
+                                     long long bs32, void* stream) {
+  const void* n = r32;
+  if (!p || !x || !r || !r32 || !scalars || !sb || !part || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32) ||
+      !pcg_tab_ok(ktab, ntab, pid) || x == p || r == p || x == r || n == p || n == x || n == r)
+    return FEA_EINVAL;
+  PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
+  g.v = p; g.x = x; g.r = r; g.r32 = r32; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars; g.sb = sb;
+  g.part = part;
+  pcg_launch<double, kPcgUpdate, true>(g, B, stream);
+  FEA_LAUNCH_CHECK();
+}

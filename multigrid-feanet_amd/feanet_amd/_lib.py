@@ -87,6 +87,11 @@ _EXTRA = {
     "fea_dd_copy_rects": ([P, I, I, P], I),
     "fea_pcg_parts": ([I, I, I], LL),
     "fea_pcg_scalar_step": ([P, LL, P, P, I, I, I, P], I),
+    # fp64 Krylov fields with an fp32 preconditioner: (..., B, H, W, ld, bstride, ld32, bstride32, stream)
+    "fea_pcg_narrow_f64f32": ([P, P, P, P, I, I, I, I, LL, I, LL, P], I),
+    "fea_pcg_dot_f64f32": ([P, P, P, I, I, I, I, LL, I, LL, P], I),
+    "fea_pcg_direction_f64f32": ([P, P, P, P, P, I, P, P, I, I, I, I, LL, I, LL, P], I),
+    "fea_pcg_update_f64f32": ([P, P, P, P, P, P, I, P, P, P, I, I, I, I, LL, I, LL, P], I),
     "fea_stencil_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),
     "fea_stencil_weight_grad_ws_bytes_f64": ([I, I, I, I], ctypes.c_size_t),
     "fea_transfer_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),

@@ -17,18 +17,26 @@ p ping-pongs between two buffers (the direction kernel rebuilds p' on its halos 
 (alpha = beta = 0, x and r stop moving, history rows repeat) once ||r|| <= its threshold or on a breakdown
 (pAp <= 0 or non-finite, r.z non-finite), so its result depends neither on the other samples nor on how often the
 host looks at the flags.  Blocks of iterations are replayed as HIP graphs.
+
+Mixed precision (dtype=float64, precond_dtype=float32): the recurrences above stay in fp64 — they fix the attainable
+accuracy — while M, which only has to be a good approximate inverse, is an fp32 hierarchy at half the bytes.  x, b, r
+and the two p are the only fp64 fields; the fp64f32 kernels hand the preconditioner float(r s_b) in its fp32 frame
+and read its fp32 end iterate.  s_b is one power of two per sample, fixed by load() so that ||r0|| s_b is in [1, 2):
+the fp32 cycle sees O(1) data however far r has been reduced and whatever the units of b, and CG is invariant to it
+(z, r.z and alpha carry the factor; x, r, beta and the history do not).
 """
 import numpy as np
 import torch
 
 from . import _lib, mesh_setup as ms, ops
-from .solver import MultigridSolver
+from .solver import MultigridSolver, _Level
 
 # scalar block layout and steps: include/feanet_hip.h (FEA_PCG_*)
 NSCALARS = 12
 RZ, RZ_PREV, PAP, ALPHA, BETA, RNORM, DONE, ITERS, EPS, RTOL, THRESH, ROW = range(NSCALARS)
 CONVERGED, BREAKDOWN = 1, 2
 STEP_INIT, STEP_RZ, STEP_PAP, STEP_RR = range(4)
+_KRYLOV = ("pcg_residual", "pcg_dot", "pcg_direction", "pcg_update")  # launched in the solver's dtype
 
 
 class PCGSolver:
@@ -38,6 +46,9 @@ class PCGSolver:
         nu: pre- and post-sweeps of the preconditioning V(nu, nu) cycle (equal, so the cycle is symmetric).
         graph: replay blocks of iterations as HIP graphs.
         check_every: solve() reads the samples' done flags every this many iterations, and at no other time.
+        precond_dtype: dtype of the preconditioning hierarchy.  None or dtype: the whole solver in dtype.
+            dtype=float64 with precond_dtype=float32: fp64 conjugate gradients around an fp32 V-cycle (five fp64
+            fine-level fields, no fp64 coarse level).  A preconditioner wider than the solve is refused.
 
     Rejected with ValueError, because the preconditioner would not be symmetric: compat schedules, the learned
     smoother, and R / P tables that are not one kernel repeated with R == P (per-pattern learned tables pick the
@@ -50,7 +61,14 @@ class PCGSolver:
 
     def __init__(self, n, levels=None, problem="poisson", dtype=torch.float64, device=None, batch=1,
                  omega=2.0 / 3.0, size=2.0, prop=(1, 20), shape=0, rows=None, R=None, P=None, w=(1.0, 1.0), nu=1,
-                 graph=True, check_every=8, smoother="jac", compat=None):
+                 graph=True, check_every=8, smoother="jac", compat=None, precond_dtype=None):
+        pdt = dtype if precond_dtype is None else precond_dtype
+        for name, d in (("dtype", dtype), ("precond_dtype", pdt)):
+            if d not in (torch.float32, torch.float64):
+                raise TypeError(f"PCGSolver: {name} must be torch.float32 or torch.float64, got {d!r}")
+        if pdt == torch.float64 and dtype == torch.float32:
+            raise ValueError("PCGSolver: precond_dtype=float64 is wider than dtype=float32; the preconditioner may be "
+                             "narrower than the solve, not wider")
         if compat is not None:
             raise ValueError("PCGSolver: compat schedules are not symmetric V-cycles")
         if smoother != "jac":
@@ -69,16 +87,30 @@ class PCGSolver:
         wl = [float(v) for v in (w.detach().cpu().tolist() if torch.is_tensor(w) else w)]
         if not (wl[0] > 0 and wl[1] > 0):
             raise ValueError("PCGSolver: the ratios w must be positive")
-        self.mg = MultigridSolver(n, levels=levels, problem=problem, dtype=dtype, device=device, batch=batch,
+        self.mg = MultigridSolver(n, levels=levels, problem=problem, dtype=pdt, device=device, batch=batch,
                                   omega=omega, size=size, prop=prop, shape=shape, R=R, P=P, w=w, nu1=int(nu),
                                   nu2=int(nu), graph=False, rows=rows, zero_start=True, smoother="jac")
         mg = self.mg
-        self.device, self.dtype, self.B = mg.device, mg.dtype, mg.B
+        self.device, self.dtype, self.B = mg.device, dtype, mg.B
+        self.mixed = pdt != dtype
         self.use_graph = bool(graph)
         self.check_every = int(check_every)
-        L0 = mg.levels[0]
-        self.r = L0.f  # the preconditioner's right-hand side buffer is the residual
-        self.x, self.b, p0, p1 = (torch.zeros_like(L0.a) for _ in range(4))
+        self._pf = mg.levels[0].f  # the preconditioner's right-hand side buffer
+        if self.mixed:
+            # the Krylov fields' own fp64 frame: its three fields are r, x and b, and its pattern map and stencil
+            # table are kapply<double>'s (pattern windows hold byte offsets of sizeof(T) table rows)
+            self.L0 = L0 = _Level(mg.m, mg.n, self.B, dtype, self.device,
+                                  pid_shape=(shape, size) if problem == "interface" else None)
+            self.ktab = torch.from_numpy(mg.ktab_np.reshape(-1, 9).astype(np.float64)).to(self.device)
+            self.r, self.x, self.b = L0.f, L0.a, L0.b
+            p0, p1 = (torch.zeros_like(L0.a) for _ in range(2))
+            self.sb = torch.ones(self.B, dtype=torch.float64, device=self.device)  # per-sample scale s_b
+            self._bc = None
+        else:
+            self.L0 = L0 = mg.levels[0]
+            self.ktab = mg.ktab
+            self.r = L0.f  # the preconditioner's right-hand side buffer is the residual
+            self.x, self.b, p0, p1 = (torch.zeros_like(L0.a) for _ in range(4))
         self.p = (p0, p1)
         self._parity = 0  # the next iteration reads p[_parity] and writes p[1 - _parity]
         self._zname = None
@@ -105,22 +137,49 @@ class PCGSolver:
         """The assembled right-hand side f, or the nodal source F (FNet applied on the device)."""
         if (f is None) == (F is None):
             raise ValueError("PCGSolver.set_rhs: give exactly one of f (assembled) or F (source)")
-        mg = self.mg
         if F is not None:
-            f = ops.conv3x3(mg._check_field(F, "F"), torch.from_numpy(mg.mass))
-        mg._pack(mg._check_field(f, "f"), self.b, reset=False)
+            f = ops.conv3x3(self._check_field(F, "F"), torch.from_numpy(self.mg.mass))
+        self._pack(self._check_field(f, "f"), self.b, reset=False)
         self._loaded = False
 
     def set_boundary(self, bc_value=None, geometry_idx=None):
         """Dirichlet data of the fine level (square geometry only, as MultigridSolver); used by the next load()."""
-        self.mg.set_boundary(bc_value, geometry_idx)
+        if not self.mixed:
+            self.mg.set_boundary(bc_value, geometry_idx)
+            return
+        self.mg.set_boundary(None, geometry_idx)  # refuses any geometry but the square; the values stay in fp64 here
+        self._bc = None if bc_value is None else self._check_field(bc_value, "boundary_value")
+
+    def _check_field(self, x, name):
+        """x as a contiguous [B, 1, H, W] tensor of the solver's dtype (never through the preconditioner's)."""
+        if not self.mixed:
+            return self.mg._check_field(x, name)
+        ops.require_hip(x, name)
+        x = x.to(self.dtype)
+        H, W = self.H, self.W
+        if x.numel() == H * W:
+            x = x.reshape(1, 1, H, W).expand(self.B, 1, H, W)
+        if tuple(x.shape[-2:]) != (H, W) or x.numel() != self.B * H * W:
+            raise ValueError(f"PCGSolver: {name} must be [{self.B}, 1, {H}, {W}]")
+        return x.reshape(self.B, 1, H, W).contiguous()
+
+    def _pack(self, x, dst, bc=None, reset=True):
+        """x (None: zeros) -> framed dst in the solver's dtype; reset: x*geo + bc, else a raw copy."""
+        bp, bs = (None, 0) if bc is None else (bc.data_ptr(), self.H * self.W)
+        _lib.call("mg_pack", self.dtype, None if x is None else x.data_ptr(), dst.data_ptr(), None,
+                  0 if reset else -1, bp, bs, *self.L0.geom(), self._stream())
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _kargs(self):
-        mg, L0 = self.mg, self.mg.levels[0]
-        return (None if L0.pid is None else L0.pid.data_ptr(), mg.ktab.data_ptr(), mg.ntab)
+        L0 = self.L0
+        return (None if L0.pid is None else L0.pid.data_ptr(), self.ktab.data_ptr(), self.mg.ntab)
+
+    def _g32(self):
+        """(ld, bstride) of the preconditioner's fp32 level-0 frame (mixed precision)."""
+        P0 = self.mg.levels[0]
+        return (P0.ld, P0.bs)
 
     def _scalar(self, step):
         return ("pcg_scalar_step", (self.part.data_ptr(), self.per, self.sc.data_ptr(), self.hist.data_ptr(),
@@ -129,18 +188,18 @@ class PCGSolver:
     def _launch(self, launches):
         stream = self._stream()
         for name, args in launches:
-            if name == "pcg_scalar_step":
+            if name == "pcg_scalar_step" or name.endswith("_f64f32"):
                 _lib.call_raw(name, *args, stream)
-            else:
-                _lib.call(name, self.dtype, *args, stream)
+            else:  # the preconditioner's plan runs in its own dtype
+                _lib.call(name, self.dtype if name in _KRYLOV else self.mg.dtype, *args, stream)
 
     def load(self, u0=None, eps=0.0, rtol=None):
         """Start from u0 (reset_boundary applied: u*geo + bc): r = b - K x, history row 0 = ||r0||.  Samples stop at
         ||r|| <= rtol * ||r0|| if rtol is given, else at ||r|| <= eps."""
-        mg, L0 = self.mg, self.mg.levels[0]
+        mg, L0 = self.mg, self.L0
         if u0 is not None:
-            u0 = mg._check_field(u0, "u0")
-        mg._pack(u0, self.x, bc=getattr(mg, "_bc", None))
+            u0 = self._check_field(u0, "u0")
+        self._pack(u0, self.x, bc=self._bc if self.mixed else getattr(mg, "_bc", None))
         self.p[0].zero_()
         self.p[1].zero_()
         self.sc.zero_()
@@ -149,19 +208,29 @@ class PCGSolver:
         self._parity = 0
         self._launch([("pcg_residual", (self.x.data_ptr(), self.b.data_ptr(), self.r.data_ptr()) + self._kargs() +
                        (self.part.data_ptr(),) + L0.geom()), self._scalar(STEP_INIT)])
+        if self.mixed:  # fixes s_b from ||r0|| and hands the preconditioner float(r0 s_b)
+            self._launch([("pcg_narrow_f64f32", (self.r.data_ptr(), self._pf.data_ptr(), self.sc.data_ptr(),
+                                                 self.sb.data_ptr()) + L0.geom() + self._g32())])
         self._loaded = True
 
     # ------------------------------------------------------------------ iteration
     def _iteration(self, q):
         """Launches of one iteration reading p[q], writing p[1 - q]."""
-        mg, L0 = self.mg, self.mg.levels[0]
+        mg, L0, P0 = self.mg, self.L0, self.mg.levels[0]
         plan, end = mg._plan("a")  # from a zero guess: the plan does not depend on the start buffer
         if self._zname is None:
             self._zname = end
-        assert end == self._zname and L0.buf(end).data_ptr() != self.r.data_ptr(), "the preconditioner's output moved"
-        z = L0.buf(end).data_ptr()
+        assert end == self._zname and P0.buf(end).data_ptr() != self._pf.data_ptr(), "the preconditioner's output moved"
+        z = P0.buf(end).data_ptr()
         g, ka, part, sc = L0.geom(), self._kargs(), self.part.data_ptr(), self.sc.data_ptr()
         pin, pout = self.p[q].data_ptr(), self.p[1 - q].data_ptr()
+        if self.mixed:
+            g = g + self._g32()
+            return list(plan) + [
+                ("pcg_dot_f64f32", (self.r.data_ptr(), z, part) + g), self._scalar(STEP_RZ),
+                ("pcg_direction_f64f32", (z, pin, pout) + ka + (sc, part) + g), self._scalar(STEP_PAP),
+                ("pcg_update_f64f32", (pout, self.x.data_ptr(), self.r.data_ptr(), self._pf.data_ptr()) + ka +
+                 (sc, self.sb.data_ptr(), part) + g), self._scalar(STEP_RR)]
         return list(plan) + [
             ("pcg_dot", (self.r.data_ptr(), z, part) + g), self._scalar(STEP_RZ),
             ("pcg_direction", (z, pin, pout) + ka + (sc, part) + g), self._scalar(STEP_PAP),
@@ -202,14 +271,14 @@ class PCGSolver:
 
     def solution(self):
         """Current iterate as a contiguous [B, 1, H, W] tensor."""
-        L0 = self.mg.levels[0]
+        L0 = self.L0
         out = torch.empty((self.B, 1, self.H, self.W), dtype=self.dtype, device=self.device)
         _lib.call("mg_unpack", self.dtype, self.x.data_ptr(), out.data_ptr(), *L0.geom(), self._stream())
         return out
 
     def residual_norm(self):
         """Per-sample true residual ||(b - K x)[1:-1, 1:-1]||_2 (float64 device tensor [B]), recomputed from x."""
-        mg, L0 = self.mg, self.mg.levels[0]
+        mg, L0 = self.mg, self.L0
         _lib.call("mg_residual_norm", self.dtype, self.x.data_ptr(), self.b.data_ptr(), *self._kargs(),
                   mg.norm_out.data_ptr(), mg.ws.data_ptr(), *L0.geom(), 0, 0, 0, 0, self._stream())
         return mg.norm_out.clone()
