@@ -27,9 +27,6 @@ constexpr int kTailMaxLevels = 8;
 constexpr int kTailMaxN = 65;  // per dimension
 constexpr int kTailLdsBytes = 160 * 1024 - 1024;
 constexpr int kTS = 10;  // table stride (9 weights + omega/d)
-#ifndef FEA_KSYM  // two-material K from the centre's table row (see framed_ops.hip kapply)
-#define FEA_KSYM 1
-#endif
 
 #ifdef FEA_TAIL_TRACE  // lab builds only (tools/lab/tail_lab.py): a timestamp after every barrier
 __device__ long long g_tail_trace[256];
@@ -101,11 +98,7 @@ constexpr int kTailDownRows = (31 + kTailThreads / 64 - 1) / (kTailThreads / 64)
 //                                                                                   Hc - 2 <= 31 (2 over 16 waves)
 constexpr int kTailUpRows = (63 + kTailThreads / 64 - 1) / (kTailThreads / 64);  // fine rows per wave going up / at the
 //                                                                                 coarsest level: H - 2 <= 63 (4)
-// FEA_TAIL_LATE_SYNC: the two-material 65^2 tail takes its staging barrier inside the first phase (down_rows SYNC)
-#ifndef FEA_TAIL_LATE_SYNC
-#define FEA_TAIL_LATE_SYNC 1
-#endif
-constexpr bool kTailLateSync = FEA_TAIL_LATE_SYNC != 0;
+// (the two-material 65^2 tail takes its staging barrier inside the first phase: down_rows SYNC)
 
 // HT != 0: the grid is HT x HT with NLEV levels, known at compile time (every BASELINE configuration
 // ends in the 65^2 .. 3^2 tail), so level sizes, offsets and rows per wave fold into immediates.
@@ -163,7 +156,7 @@ struct TailFast {
   __device__ __forceinline__ T Kx(int j, const T (&xl)[R], const T (&x)[R], const T (&xr)[R], const int (&ql)[R],
                                   const int (&q)[R], const int (&qr)[R]) const {
     T acc = 0;
-    if constexpr (MULTI && FEA_KSYM) {  // the centre's table row, mirrored taps (framed_ops.hip kapply): same bits
+    if constexpr (MULTI) {  // the centre's table row, mirrored taps (framed_strip.h kapply)
 #pragma unroll
       for (int dr = 0; dr < 3; ++dr) {
         acc += kw(q[j], 8 - dr * 3) * xl[j - 1 + dr];
@@ -173,7 +166,7 @@ struct TailFast {
       return acc;
     }
 #pragma unroll
-    for (int dr = 0; dr < 3; ++dr) {
+    for (int dr = 0; dr < 3; ++dr) {  // one pattern: kw() is kr[d]
       acc += kw(ql[j - 1 + dr], dr * 3 + 0) * xl[j - 1 + dr];
       acc += kw(q[j - 1 + dr], dr * 3 + 1) * x[j - 1 + dr];
       acc += kw(qr[j - 1 + dr], dr * 3 + 2) * xr[j - 1 + dr];
@@ -266,7 +259,7 @@ struct TailFast {
     const int Hc = (Hk(k) + 1) / 2;
     const int per = (Hc - 2 + kWaves - 1) / kWaves;  // <= kTailDownRows
     const int I0 = 1 + wv * per, I1 = min(Hc - 1, I0 + per);
-    if constexpr (GLOBAL && MULTI && HT == 65 && kTailLateSync) {  // 31 coarse rows: every wave has two
+    if constexpr (GLOBAL && MULTI && HT == 65) {  // 31 coarse rows: every wave has two
       down_rows<true, kTailDownRows, true>(k, o, I0, I1);
       return;
     }
@@ -526,8 +519,8 @@ __global__ __launch_bounds__(kTailThreads) void k_mg_coarse_tail(TailArgs<T> a) 
   }
   if constexpr (FIX65) {
     // the first down phase reads f_t from HBM itself and stages it for the up phase; single pattern:
-    // the tables come from uniform loads, so nothing has to land before it
-    if (MULTI && !kTailLateSync) FEA_TAIL_SYNC();  // (else the first phase takes it after its HBM loads)
+    // the tables come from uniform loads, so nothing has to land before it (two materials: the first phase takes
+    // the barrier after its HBM loads)
     tail_fast<T, MULTI, 65, 6>(a, va, fs, ktb, rtb, ptb, pl, wv, lane
 #ifdef FEA_TAIL_TRACE
                                , nph
@@ -931,56 +924,61 @@ static inline bool tail_dim_ok(int n, int nlev) {
   return true;
 }
 
-#define FEA_TAIL_API(SUF, T)                                                                                  \
-  extern "C" int fea_mg_coarse_tail_##SUF(const T* f_t, T* v_t, int Ht, int Wt, int nlev, int ld_t,          \
-                                          long long bs_t,                                                      \
-                                          const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab,    \
-                                          const T* rtab, const T* ptab, T w0, T w1, int nu1, int nu2, int q2,  \
-                                          int B, void* stream) {                                               \
-    if (!f_t || !v_t || !ktab || !omd || !rtab || !ptab || B <= 0 || nlev < 1 || nlev > kTailMaxLevels)       \
-      return FEA_EINVAL;                                                                                      \
-    if (!tail_dim_ok(Ht, nlev) || !tail_dim_ok(Wt, nlev) || nu1 < 0 || nu2 < 0) return FEA_EINVAL;           \
-    const bool multi = ntab > 1;                                                                              \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (multi && !pid_levels)) return FEA_EINVAL;                     \
-    if (tail_lds_bytes<T>(Ht, Wt, nlev, multi) > kTailLdsBytes) return FEA_EINVAL;                           \
-    TailArgs<T> a{f_t, v_t, pid_levels, ktab, omd, rtab, ptab, w0, w1, Ht, Wt, nlev, ld_t, bs_t, ntab, nu1, nu2,  \
-                  q2};                                                                                        \
-    const bool fix65 = Ht == 65 && Wt == 65 && nlev == 6 && nu1 == 1 && nu2 == 1 && !q2;                     \
-    hipStream_t s_ = (hipStream_t)stream;                                                                     \
-    const bool v11 = nu1 == 1 && nu2 == 1 && !q2;                                                             \
-    if (multi && fix65) k_mg_coarse_tail<T, true, true><<<B, kTailThreads, 0, s_>>>(a);                       \
-    else if (multi && v11) k_mg_coarse_tail<T, true, false, true><<<B, kTailThreads, 0, s_>>>(a);             \
-    else if (multi) k_mg_coarse_tail<T, true><<<B, kTailThreads, 0, s_>>>(a);                                  \
-    else if (fix65) k_mg_coarse_tail<T, false, true><<<B, kTailThreads, 0, s_>>>(a);                          \
-    else if (v11) k_mg_coarse_tail<T, false, false, true><<<B, kTailThreads, 0, s_>>>(a);                     \
-    else k_mg_coarse_tail<T, false><<<B, kTailThreads, 0, s_>>>(a);                                            \
-    FEA_LAUNCH_CHECK();                                                                                       \
-  }
+template <typename T>
+static int coarse_tail(const T* f_t, T* v_t, int Ht, int Wt, int nlev, int ld_t, long long bs_t,
+                       const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab, const T* rtab, const T* ptab,
+                       T w0, T w1, int nu1, int nu2, int q2, int B, void* stream) {
+  if (!f_t || !v_t || !omd || !rtab || !ptab || B <= 0 || nlev < 1 || nlev > kTailMaxLevels) return FEA_EINVAL;
+  if (!tail_dim_ok(Ht, nlev) || !tail_dim_ok(Wt, nlev) || nu1 < 0 || nu2 < 0) return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (!tab_ok(ktab, ntab, pid_levels)) return FEA_EINVAL;
+  if (tail_lds_bytes<T>(Ht, Wt, nlev, multi) > kTailLdsBytes) return FEA_EINVAL;
+  TailArgs<T> a{f_t, v_t, pid_levels, ktab, omd, rtab, ptab, w0, w1, Ht, Wt, nlev, ld_t, bs_t, ntab, nu1, nu2, q2};
+  const bool v11 = nu1 == 1 && nu2 == 1 && !q2;
+  const bool fix65 = Ht == 65 && Wt == 65 && nlev == 6 && v11;
+  hipStream_t s_ = (hipStream_t)stream;
+  if (multi && fix65) k_mg_coarse_tail<T, true, true><<<B, kTailThreads, 0, s_>>>(a);
+  else if (multi && v11) k_mg_coarse_tail<T, true, false, true><<<B, kTailThreads, 0, s_>>>(a);
+  else if (multi) k_mg_coarse_tail<T, true><<<B, kTailThreads, 0, s_>>>(a);
+  else if (fix65) k_mg_coarse_tail<T, false, true><<<B, kTailThreads, 0, s_>>>(a);
+  else if (v11) k_mg_coarse_tail<T, false, false, true><<<B, kTailThreads, 0, s_>>>(a);
+  else k_mg_coarse_tail<T, false><<<B, kTailThreads, 0, s_>>>(a);
+  return launch_status();
+}
 
+template <typename T>
+static int coarse_tail_ext(const T* f_x, T* v_x, int Hx, int Wx, int ld_x, long long bs_x, int nlev, const T* ktab,
+                           const T* omd, int ntab, const T* rtab, const T* ptab, T w0, T w1, int B, void* stream) {
+  if (!f_x || !v_x || !ktab || !omd || !rtab || !ptab || B <= 0 || nlev < 1 || nlev > kTailMaxLevels)
+    return FEA_EINVAL;
+  if (ntab != 1 || Hx < 5 || Wx < 5 || !(Hx & 1) || !(Wx & 1)) return FEA_EINVAL;
+  const int Ht = (Hx + 1) / 2, Wt = (Wx + 1) / 2;
+  if (!tail_dim_ok(Ht, nlev) || !tail_dim_ok(Wt, nlev)) return FEA_EINVAL;
+  if (ld_x < Wx + 128 / (int)sizeof(T) || bs_x < (long long)(Hx + 2) * ld_x) return FEA_EINVAL;
+  if (tail_lds_bytes<T>(Ht, Wt, nlev, false) > kTailLdsBytes) return FEA_EINVAL;
+  TailArgs<T> a{f_x, v_x, nullptr, ktab, omd, rtab, ptab, w0, w1, Ht, Wt, nlev, ld_x, bs_x, 1, 1, 1, 0};
+  ExtArgs<T> x{f_x, v_x, Hx, Wx, ld_x, bs_x};
+  hipStream_t s_ = (hipStream_t)stream;
+  if (Ht == 65 && Wt == 65 && nlev == 6) k_mg_coarse_tail_ext<T, true><<<B, kTailThreads, 0, s_>>>(a, x);
+  else k_mg_coarse_tail_ext<T, false><<<B, kTailThreads, 0, s_>>>(a, x);
+  return launch_status();
+}
+
+#define FEA_TAIL_API(SUF, T)                                                                                      \
+  extern "C" int fea_mg_coarse_tail_##SUF(const T* f_t, T* v_t, int Ht, int Wt, int nlev, int ld_t, long long bs_t, \
+                                          const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab,        \
+                                          const T* rtab, const T* ptab, T w0, T w1, int nu1, int nu2, int q2,      \
+                                          int B, void* stream) {                                                   \
+    return coarse_tail<T>(f_t, v_t, Ht, Wt, nlev, ld_t, bs_t, pid_levels, ktab, omd, ntab, rtab, ptab, w0, w1, nu1, \
+                          nu2, q2, B, stream);                                                                     \
+  }                                                                                                               \
+  extern "C" int fea_mg_coarse_tail_ext_##SUF(const T* f_x, T* v_x, int Hx, int Wx, int ld_x, long long bs_x,      \
+                                              int nlev, const T* ktab, const T* omd, int ntab, const T* rtab,      \
+                                              const T* ptab, T w0, T w1, int B, void* stream) {                    \
+    return coarse_tail_ext<T>(f_x, v_x, Hx, Wx, ld_x, bs_x, nlev, ktab, omd, ntab, rtab, ptab, w0, w1, B, stream);  \
+  }
 FEA_TAIL_API(f32, float)
 FEA_TAIL_API(f64, double)
-
-#define FEA_TAIL_EXT_API(SUF, T)                                                                              \
-  extern "C" int fea_mg_coarse_tail_ext_##SUF(const T* f_x, T* v_x, int Hx, int Wx, int ld_x, long long bs_x,  \
-                                              int nlev, const T* ktab, const T* omd, int ntab, const T* rtab,   \
-                                              const T* ptab, T w0, T w1, int B, void* stream) {                \
-    if (!f_x || !v_x || !ktab || !omd || !rtab || !ptab || B <= 0 || nlev < 1 || nlev > kTailMaxLevels)       \
-      return FEA_EINVAL;                                                                                      \
-    if (ntab != 1 || Hx < 5 || Wx < 5 || !(Hx & 1) || !(Wx & 1)) return FEA_EINVAL;                            \
-    const int Ht = (Hx + 1) / 2, Wt = (Wx + 1) / 2;                                                           \
-    if (!tail_dim_ok(Ht, nlev) || !tail_dim_ok(Wt, nlev)) return FEA_EINVAL;                                  \
-    if (ld_x < Wx + 128 / (int)sizeof(T) || bs_x < (long long)(Hx + 2) * ld_x) return FEA_EINVAL;              \
-    if (tail_lds_bytes<T>(Ht, Wt, nlev, false) > kTailLdsBytes) return FEA_EINVAL;                            \
-    TailArgs<T> a{f_x, v_x, nullptr, ktab, omd, rtab, ptab, w0, w1, Ht, Wt, nlev, ld_x, bs_x, 1, 1, 1, 0};       \
-    ExtArgs<T> x{f_x, v_x, Hx, Wx, ld_x, bs_x};                                                               \
-    hipStream_t s_ = (hipStream_t)stream;                                                                     \
-    if (Ht == 65 && Wt == 65 && nlev == 6) k_mg_coarse_tail_ext<T, true><<<B, kTailThreads, 0, s_>>>(a, x);     \
-    else k_mg_coarse_tail_ext<T, false><<<B, kTailThreads, 0, s_>>>(a, x);                                    \
-    FEA_LAUNCH_CHECK();                                                                                       \
-  }
-
-FEA_TAIL_EXT_API(f32, float)
-FEA_TAIL_EXT_API(f64, double)
 
 #ifdef FEA_TAIL_TRACE
 extern "C" int fea_tail_trace_read(long long* host) {

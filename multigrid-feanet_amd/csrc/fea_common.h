@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "feanet_hip.h"
 
@@ -119,8 +120,30 @@ static __global__ __launch_bounds__(256) void k_norm_final(const double* __restr
 
 }  // namespace fea
 
-#define FEA_LAUNCH_CHECK()                   \
-  do {                                       \
-    hipError_t _e = hipGetLastError();       \
-    return _e == hipSuccess ? 0 : (int)_e;   \
-  } while (0)
+// ---------------------------------------------------------------------------
+// Host launch layer: what every entry point's launcher shares.
+// ---------------------------------------------------------------------------
+// the return value of an entry point after its launches: 0 or the hipError_t
+static inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+// Stencil (or transfer) table rule: a table, 1..FEA_MAX_PATTERNS rows, and a pattern map when there is more than one.
+static inline bool tab_ok(const void* tab, int ntab, const void* pid) {
+  return tab && ntab >= 1 && ntab <= FEA_MAX_PATTERNS && (ntab == 1 || pid);
+}
+// A transfer table (restriction, prolongation) next to the stencil table: one row per stencil pattern (of the counts
+// 1 and ntab, 1 is taken only with one pattern: no kernel shares a single row among several patterns).
+static inline bool xtab_ok(int nx, int ntab) { return nx == ntab; }
+
+// Runtime flags as compile-time arguments: f(std::bool_constant<flags>...), f a generic lambda that launches the
+// kernel instantiation of its arguments.  A lambda that skips a combination with `if constexpr` does not
+// instantiate that kernel.
+template <typename F>
+static inline void with_flags(F&& f) { f(); }
+template <typename F, typename... B>
+static inline void with_flags(F&& f, bool b, B... rest) {
+  if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}

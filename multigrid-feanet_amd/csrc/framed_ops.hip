@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void k_mg_resid_restrict(MgArgs<T> g) {
     }
     T* cp = cb + (long long)(I + 1) * g.ldc;
     if (Jl + Q - 1 <= Wc - 2) {
-      vstore<T, Q, kCoarseNT && NT>(cp, o);
+      vstore<T, Q>(cp, o);
     } else {
 #pragma unroll
       for (int q = 0; q < Q; ++q)
@@ -550,7 +550,7 @@ __device__ __forceinline__ void sweep_restrict_task(const MgArgs<T>& g, const Ta
     if (!own) return;
     T* cp = cb + (long long)(I + 1) * g.ldc;
     if (J0 + Q - 1 <= Wc - 2) {
-      vstore<T, Q, kCoarseNT && NT>(cp, o);
+      vstore<T, Q>(cp, o);
     } else {
 #pragma unroll
       for (int q = 0; q < Q; ++q)
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(256) void k_mg_zero_restrict(MgArgs<T> g) {
     if (own) {
       T* cp = cb + (long long)(I + 1) * g.ldc;
       if (J0 + Q - 1 <= Wc - 2) {
-        vstore<T, Q, kCoarseNT && NT>(cp, o);
+        vstore<T, Q>(cp, o);
       } else {
 #pragma unroll
         for (int q = 0; q < Q; ++q)
@@ -811,13 +811,9 @@ struct Ovl2 {
   static constexpr int S = ((64 * V - 6 - HLC) / 4) * 4;     // owned fine columns per strip (fp64 116, fp32 244)
 };
 
-// ZR2 ALT: odd row tasks stream bottom-up, so two vertically adjacent tasks reach the fine rows both load
+// Odd row tasks stream bottom-up, so two vertically adjacent tasks reach the fine rows both load
 // (3 + 1 rows of the intermediate level are recomputed per task) at the same moment — both at their start
 // or both at their end — and the second read of those rows is an L2 hit (k_mg_cycle_join does the same).
-#ifndef FEA_ZR2_ALT
-#define FEA_ZR2_ALT 1
-#endif
-constexpr bool kZr2Alternate = FEA_ZR2_ALT != 0;
 
 // One row task of k_mg_zero_restrict2.  REV: rows are streamed bottom-up (row step S = -1); every node value
 // is the same expression as in the forward task: stencil windows are passed in grid order, and each
@@ -1097,7 +1093,7 @@ __global__ __launch_bounds__(256) void k_mg_zero_restrict2(MgArgs<T> g) {
   }
   const TaskId id = decode_task_lin(g.nstrips, g.ntr);
   if (!id.valid) return;
-  if (kZr2Alternate && (id.t & 1)) zr2_task<T, MULTI, true>(g, id, tab, rtb);
+  if (id.t & 1) zr2_task<T, MULTI, true>(g, id, tab, rtb);
   else zr2_task<T, MULTI, false>(g, id, tab, rtb);
 }
 
@@ -1592,12 +1588,8 @@ struct Ovl4 {
   static constexpr int S = 59 * V;      // owned fine columns per strip (fp64 118, fp32 236)
 };
 
-// PROLONG2 ALT: odd row tasks stream bottom-up (REV), so vertically adjacent tasks read the rows they share (the
+// Odd row tasks stream bottom-up (REV), so vertically adjacent tasks read the rows they share (the
 // fine halo row, the coarse stage's extra rows) at the same moment and the second read is an L2 hit.
-#ifndef FEA_PROLONG2_ALT
-#define FEA_PROLONG2_ALT 1
-#endif
-constexpr bool kProlong2Alternate = FEA_PROLONG2_ALT != 0;
 
 template <typename T, bool MULTI, bool REV>
 __device__ __forceinline__ void prolong2_task(const MgArgs<T>& g, const TaskId& id, const T* tab, const T* ptb) {
@@ -1925,7 +1917,7 @@ __global__ __launch_bounds__(256) void k_mg_prolong2(MgArgs<T> g) {
   if (!id.valid) return;
   // fp64 only: the reversed task body needs ~150 VGPRs (fp32 forward: 100, 4 waves per SIMD), which costs the
   // batched fp32 cycles (C5: 52 instead of 42 us) more than the L2 reuse gains; fp64 gains 1 us at 4097^2
-  if constexpr (kProlong2Alternate && sizeof(T) == 8) {
+  if constexpr (sizeof(T) == 8) {
     if (id.t & 1) {
       prolong2_task<T, MULTI, true>(g, id, tab, ptb);
       return;
@@ -1953,25 +1945,17 @@ __device__ __forceinline__ X& pick(X& a, X& b) {
   else return a;
 }
 
-// cycle join: input rows in flight per wave (2 or 4) and the occupancy the register budget is held to
-// (0: the compiler's choice).  A/B on MI355X (tools/lab/ab_bench.sh, V-cycle): 2 rows, free budget
-// (144 VGPRs, 3 waves/SIMD) 196.6 us; 4 rows at 3 waves (spills) 199.3 us; 4 rows at 2 waves 206.0 us.
+// cycle join: input rows in flight per wave (2 or 4); the register budget is the compiler's choice.  A/B on MI355X
+// (tools/lab/ab_bench.sh, V-cycle): 2 rows, free budget (144 VGPRs, 3 waves/SIMD) 196.6 us; 4 rows held to 3 waves
+// (spills) 199.3 us; 4 rows at 2 waves 206.0 us.
 #ifndef FEA_JOIN_AHEAD
 #define FEA_JOIN_AHEAD 2
-#endif
-#ifndef FEA_JOIN_WAVES
-#define FEA_JOIN_WAVES 0
 #endif
 static_assert(FEA_JOIN_AHEAD == 2 || FEA_JOIN_AHEAD == 4, "join prefetch ring of 2 or 4 rows");
 #ifndef FEA_JOIN_UNROLL
 #define FEA_JOIN_UNROLL 4
 #endif
 constexpr int kJoinUnroll = FEA_JOIN_UNROLL;
-// FEA_JOIN_PEEL: fp32 joins peel the pipeline fill (compile-time stage flags); fp64 keeps runtime flags
-#ifndef FEA_JOIN_PEEL
-#define FEA_JOIN_PEEL 1
-#endif
-constexpr bool kJoinPeel = FEA_JOIN_PEEL != 0;
 static_assert(kJoinUnroll % FEA_JOIN_AHEAD == 0 && kJoinUnroll % 2 == 0, "join unroll: a multiple of the ring");
 // f(integral_constant<int, i>) for i = 0 .. N-1, in order (compile-time step positions)
 template <int N, typename Fn, int... I>
@@ -1982,50 +1966,22 @@ template <int N, typename Fn>
 __device__ __forceinline__ void unroll_steps(Fn&& fn) {
   unroll_steps_<N>(fn, std::make_integer_sequence<int, N>{});
 }
-// FEA_JOIN_NTL: nontemporal loads of the iterate u in the join on levels above the NT threshold
-#ifndef FEA_JOIN_NTL
-#define FEA_JOIN_NTL 1
-#endif
-constexpr bool kJoinNTL = FEA_JOIN_NTL != 0;
+// Streaming policy of the join.  NT (levels above the nontemporal threshold): the iterate u is loaded nontemporally
+// as well as stored so, the rows two tasks share included (loading those through the cache evicts the right-hand
+// side: 4097^2 fp64 join 95 against 82.6 us, profiles/r02_ab).
 // NTF (template flag of the join): nontemporal loads of the right-hand side f too, on levels whose fields of
 // ONE sample exceed the Infinity Cache (8193^2 fp64 join 397 -> 371 us; with many small samples, C5, it
 // costs 953 -> 980 us; same-process A/B, profiles/r03_stream/ntl_ab.txt)
-// FEA_JOIN_ALT: odd row tasks stream bottom-up (see join_task).  FEA_JOIN_SHARED: the rows two tasks
-// share are loaded through the cache instead of nontemporally (with FEA_JOIN_NTL).  Same-lease A/B at
-// 4097^2 fp64 (profiles/r02_ab): ALT=1 join 82.6 us, 348 MB read per launch; ALT=0 84.3 us, 385 MB;
-// ALT=1 SHARED=1 95 us, 336 MB (the cached rows evict the right-hand side, like NTL=0).
-#ifndef FEA_JOIN_ALT
-#define FEA_JOIN_ALT 1
-#endif
-#ifndef FEA_JOIN_SHARED
-#define FEA_JOIN_SHARED 0
-#endif
-constexpr bool kJoinAlternate = FEA_JOIN_ALT != 0;
-// FEA_JOIN_INNER (lab): interior tasks take a join_task instantiation without boundary selects / clamps (measured
-// in the ISA only: the kernel holding both instantiations needs 203-209 VGPRs, two waves per SIMD instead of three).
-// FEA_JOIN_OMZ: a sweep keeps a boundary node's value through a zero omega/d (v = 0 * r + b) instead of a select of
-// the result; the select was compiled as an exec-mask branch per node and stage (fp64 join: 3090 -> 2025 SALU,
-// 428 -> 167 branches in the kernel, 154 -> 145 VGPRs; metric V-cycle 136.8 -> 135.5 us, join 80.0 -> 79.1 us,
-// same-lease A/B twice, profiles/r05_ab/join_omz.txt).  Bitwise: on a boundary node b == the kept value (x = u + w1 P e
-// with every coarse value P reads there on the coarse boundary, i.e. zero), up to the sign of a zero.
-#ifndef FEA_JOIN_INNER
-#define FEA_JOIN_INNER 0
-#endif
-// lab builds (-DFEA_LAB_JREV): every second join launch deals its tasks in reverse order (decode_task_lin's rev) —
-// measured slower (+1.5 us per V-cycle, profiles/r05_ab/join_omz.txt)
-#ifdef FEA_LAB_JREV
-#define FEA_LAB_JOIN_REV(g) { static int flip = 0; (g).rev = flip = !flip; }
-#elif defined(FEA_LAB_JFLIP)
-#define FEA_LAB_JOIN_REV(g) { static int fl = 0; (g).flip = fl; fl ^= 1; }
-#else
-#define FEA_LAB_JOIN_REV(g)
-#endif
-#ifndef FEA_JOIN_OMZ
-#define FEA_JOIN_OMZ 1
-#endif
-constexpr bool kJoinInner = FEA_JOIN_INNER != 0;
-constexpr bool kJoinOmz = FEA_JOIN_OMZ != 0;
-#define REV_SHARED_LOADS (FEA_JOIN_SHARED != 0)
+// Odd row tasks stream bottom-up (see join_task): same-lease A/B at 4097^2 fp64 (profiles/r02_ab), join 82.6 us and
+// 348 MB read per launch against 84.3 us and 385 MB with every task top-down.
+// One join_task body serves every task: a second one without boundary selects for interior tasks brings the kernel
+// to 203-209 VGPRs, two waves per SIMD instead of three.  Dealing every second launch's tasks in reverse order
+// measured slower too (+1.5 us per V-cycle, profiles/r05_ab/join_omz.txt).
+// A sweep keeps a boundary node's value through a zero omega/d (v = 0 * r + b) instead of a select of the result,
+// which was compiled as an exec-mask branch per node and stage (fp64 join: 3090 -> 2025 SALU, 428 -> 167 branches,
+// 154 -> 145 VGPRs; metric V-cycle 136.8 -> 135.5 us, join 80.0 -> 79.1 us, same-lease A/B twice,
+// profiles/r05_ab/join_omz.txt).  Bitwise: on a boundary node b == the kept value (x = u + w1 P e with every coarse
+// value P reads there on the coarse boundary, i.e. zero), up to the sign of a zero.
 
 template <typename T>
 struct Ovl3 {
@@ -2053,10 +2009,7 @@ struct JoinTask {
   int b, t, I0, I1, c0, cmax;
 };
 
-// EDGE = false: an interior task (join_interior): every row it streams and every column its lanes load lies inside
-// the grid, so the boundary selects, the row clamps, the lane clamps and the partial stores drop out at compile
-// time (same per-node expressions: bitwise the general task).
-template <typename T, bool MULTI, bool NT, bool NORM, bool REV, bool NTF, bool EDGE = true>
+template <typename T, bool MULTI, bool NT, bool NORM, bool REV, bool NTF>
 __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt, const T* tab, const T* rtb,
                                           const T* ptb, double& ssq) {
   constexpr int kJoinAhead = MULTI ? 2 : FEA_JOIN_AHEAD;
@@ -2088,7 +2041,7 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
   const T w0 = g.w, w1 = g.w2;
   bool cin[V];
 #pragma unroll
-  for (int k = 0; k < V; ++k) cin[k] = !EDGE || (cl + k >= 1 && cl + k <= W - 2);
+  for (int k = 0; k < V; ++k) cin[k] = cl + k >= 1 && cl + k <= W - 2;
   const bool own = lane >= O::L0 && lane < O::L0 + O::OWN;
   const int J0 = (cl + 1) / 2;
   const long long boff = (long long)jt.b * g.bs + F::OFF + cs;
@@ -2104,12 +2057,9 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
   // lanes past the grid's last fine column W - 1 (coarse: Wc - 1) load the last needed lane's columns
   // again instead of streaming columns nothing uses: the last strip of a row can be mostly outside
   // the grid (25 % of the loaded columns at 1025 wide in fp32); stores are masked by column anyway
-  const int ll = EDGE ? min(lane, (W - 1 - cs) / V) : lane;
-  const int llc = EDGE ? min(lane, (Wc - 1 - (cs + 1) / 2) / Q) : lane;
-  auto rowo = [&](int r) -> long long {
-    if constexpr (EDGE) r = min(max(r, -1), H);
-    return (long long)(r + 1) * ld + V * ll;
-  };
+  const int ll = min(lane, (W - 1 - cs) / V);
+  const int llc = min(lane, (Wc - 1 - (cs + 1) / 2) / Q);
+  auto rowo = [&](int r) -> long long { return (long long)(min(max(r, -1), H) + 1) * ld + V * ll; };
   auto crowo = [&](int a) -> long long { return (long long)(min(max(a, -1), Hc) + 1) * ldc; };
   auto rc = [&](int a) {
     return raw_crow<T, V, MULTI>(eb + crowo(a), MULTI ? pcb + crowo(a) : nullptr, lane, llc);
@@ -2121,25 +2071,15 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
   Row<T, V> Wa{}, Wb{}, Wc_{}; // w windows of rows y-4s, y-3s, y-2s
   PRow<V> P4{}, P3{}, P2{}, P1{}, P0{};  // pattern windows of rows y-4s .. y
   T f1[V], f2[V], f3[V];       // f of rows y-2s, y-3s, y-4s (after the rotation at the step's end: y-s ..)
-  T um1[V];                    // u (uncorrected) of row y-s: v keeps it on boundary nodes
   T acc[Q], t2[Q];             // forward: restriction partial sum; reversed: the ky=1 and ky=2 terms
 #pragma unroll
-  for (int k = 0; k < V; ++k) f1[k] = f2[k] = f3[k] = um1[k] = T(0);
+  for (int k = 0; k < V; ++k) f1[k] = f2[k] = f3[k] = T(0);
 #pragma unroll
   for (int q = 0; q < Q; ++q) acc[q] = t2[q] = T(0);
 
   const int ys = 2 * I0 - 4, ye = 2 * I1 + 2;
   const int yb = REV ? ye : ys;  // first row streamed
-  // shared input rows (recomputed by the neighbouring task too) are loaded through the cache
-  auto shared_row = [&](int y) { return y <= ys + 6 || y >= ye - 6; };
-  auto load_u = [&](int y, T (&x)[V]) {
-    if constexpr (kJoinNTL && NT && REV_SHARED_LOADS) {
-      if (shared_row(y)) vload<T, V>(ub + rowo(y), x);
-      else vload<T, V, true>(ub + rowo(y), x);
-    } else {
-      vload<T, V, kJoinNTL && NT>(ub + rowo(y), x);
-    }
-  };
+  auto load_u = [&](int y, T (&x)[V]) { vload<T, V, NT>(ub + rowo(y), x); };
   // inputs u(y), f(y-s), pid(y) in flight kJoinAhead steps ahead, in a ring of buffers indexed by the
   // step's position mod kJoinAhead (compile-time), so no in-flight register is ever copied (a copy
   // would force the wait for its load at once) — the join runs 3 waves per SIMD and needs the
@@ -2159,33 +2099,26 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
 
   // count: add the squared residual of the input row y to ssq (NORM; the row and lane own y)
   auto sweep_own = [&](const Row<T, V>& a, const Row<T, V>& b, const Row<T, V>& c, const PRow<V>& pa,
-                       const PRow<V>& pb_, const PRow<V>& pc, const T (&fy)[V], const T (&keep)[V], int y,
-                       T (&o)[V], bool count) {
-    const bool rin = !EDGE || (y >= 1 && y <= H - 2);
+                       const PRow<V>& pb_, const PRow<V>& pc, const T (&fy)[V], int y, T (&o)[V], bool count) {
+    const bool rin = y >= 1 && y <= H - 2;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       const T acck = kapply<T, V, MULTI>(a, b, c, pa, pb_, pc, k, ks, tab);
       const T omk = MULTI ? tabv(tab, pb_.a[k + 1], 9) : om;
       const T rr = fy[k] - acck;
-      if constexpr (kJoinOmz) {
-        // boundary nodes: 0 * r + b = b, and b == keep there (the prolonged correction of a boundary node is a
-        // sum of coarse boundary values, all zero, so x = u exactly)
-        const T omz = (rin && cin[k]) ? omk : T(0);
-        o[k] = omz * rr + b.a[k + 1];
-      } else {
-        const T v = omk * rr + b.a[k + 1];
-        o[k] = (rin && cin[k]) ? v : keep[k];
-      }
+      // boundary nodes: 0 * r + b = b, the value they keep (the prolonged correction of a boundary node is a sum
+      // of coarse boundary values, all zero, so x = u exactly)
+      const T omz = (rin && cin[k]) ? omk : T(0);
+      o[k] = omz * rr + b.a[k + 1];
       if constexpr (NORM)
         if (count && rin && cin[k]) ssq += (double)rr * (double)rr;
     }
   };
   // the stencil takes its three rows in grid order (row i-1, i, i+1)
   auto sweep3 = [&](const Row<T, V>& a, const Row<T, V>& b, const Row<T, V>& c, const PRow<V>& pa,
-                    const PRow<V>& pb_, const PRow<V>& pc, const T (&fy)[V], const T (&keep)[V], int y, T (&o)[V],
-                    bool count) {
-    if constexpr (REV) sweep_own(c, b, a, pc, pb_, pa, fy, keep, y, o, count);
-    else sweep_own(a, b, c, pa, pb_, pc, fy, keep, y, o, count);
+                    const PRow<V>& pb_, const PRow<V>& pc, const T (&fy)[V], int y, T (&o)[V], bool count) {
+    if constexpr (REV) sweep_own(c, b, a, pc, pb_, pa, fy, y, o, count);
+    else sweep_own(a, b, c, pa, pb_, pc, fy, y, o, count);
   };
 
   // nn: the step index where it is < kFill (the pipeline's fill steps run stages 2 .. 4 only from step 2, 4, 6
@@ -2242,23 +2175,17 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
     // 2. v(y-s) = J(x) (boundary nodes keep u)
     if (NN >= 2) {
       T v[V];
-      sweep3(Xa, Xb, Xc, P2, P1, P0, fy1, um1, y - S, v, false);
+      sweep3(Xa, Xb, Xc, P2, P1, P0, fy1, y - S, v, false);
       Va = Vb;
       Vb = Vc;
       Vc = own_row<T, V>(v);
       // 3. w(y-2s) = J(v) (boundary nodes keep v)
       if (NN >= 4) {
-        T keep[V], w[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) keep[k] = Vb.a[k + 1];
+        T w[V];
         const int yw = y - 2 * S;
         const bool ownr = yw >= 2 * I0 - 1 && (yw < 2 * I1 - 1 || I1 == Hc - 1) && yw <= H - 2;
-        sweep3(Va, Vb, Vc, P3, P2, P1, f1, keep, yw, w, own && ownr);
-        if constexpr (EDGE) {
-          if (own && ownr) store_masked<T, V, NT>(ob + rowo(yw), w, cl, Ws);
-        } else {
-          if (own && ownr) vstore<T, V, NT>(ob + rowo(yw), w);
-        }
+        sweep3(Va, Vb, Vc, P3, P2, P1, f1, yw, w, own && ownr);
+        if (own && ownr) store_masked<T, V, NT>(ob + rowo(yw), w, cl, Ws);
         Wa = Wb;
         Wb = Wc_;
         Wc_ = own_row<T, V>(w);
@@ -2288,8 +2215,8 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
           auto put = [&](int I, const T (&o)[Q]) {
             if (own) {
               T* cp = cb + (long long)(I + 1) * ldc;
-              if (!EDGE || J0 + Q - 1 <= Wcs - 2) {
-                vstore<T, Q, kCoarseNT && NT>(cp, o);
+              if (J0 + Q - 1 <= Wcs - 2) {
+                vstore<T, Q>(cp, o);
               } else {
 #pragma unroll
                 for (int q = 0; q < Q; ++q)
@@ -2329,20 +2256,19 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
         }
       }
     }
-    // rotate f and u rows
+    // rotate f rows
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       f3[k] = f2[k];
       f2[k] = f1[k];
       f1[k] = fy1[k];
-      um1[k] = u0[k];
     }
   };
 
   // ye - ys + 1 steps (odd); the ring slot is a template argument, so the loop is unrolled by a multiple of
   // the ring: FEA_JOIN_UNROLL = 4, or 6 (= the 3-row window period x the 2-slot ring: every window rotation
   // is a register renaming inside the body and the loop's back edge needs no moves)
-  if constexpr (kJoinPeel && sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 4) {  // fp32 joins peel the pipeline fill (compile-time stage flags)
     constexpr int U = kJoinUnroll;
     using Full = std::integral_constant<int, kFill>;
     // the kFill fill steps (>= 9 steps per task: rb >= 2), then the steady state in blocks of U (the step
@@ -2376,11 +2302,7 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
 }
 
 template <typename T, bool MULTI, bool NORM, bool NT, bool NTF = false>
-__global__ __launch_bounds__(256)
-#if FEA_JOIN_WAVES > 0
-__attribute__((amdgpu_waves_per_eu(FEA_JOIN_WAVES)))
-#endif
-void k_mg_cycle_join(MgArgs<T> g) {
+__global__ __launch_bounds__(256) void k_mg_cycle_join(MgArgs<T> g) {
   __shared__ T tab[MULTI ? FEA_MAX_PATTERNS * kTabStride : 1];
   __shared__ T rtb[MULTI ? FEA_MAX_PATTERNS * kTabStride : 1];
   __shared__ T ptb[MULTI ? FEA_MAX_PATTERNS * kTabStride : 1];
@@ -2419,18 +2341,8 @@ void k_mg_cycle_join(MgArgs<T> g) {
   }
   double ssq = 0.0;
   if (valid) {
-    // interior task: rows 2 I0 - 4 .. 2 I1 + 2 inside [1, H - 2] (loads reach 2 rows further, still in the frame) and
-    // every loaded column inside [1, W - 2]
-    const int cs = jt.c0 - Ovl3<T>::HL;
-    const bool inner = kJoinInner && g.nrect == 0 && 2 * jt.I0 - 4 >= 1 && 2 * jt.I1 + 2 <= g.H - 2 && cs >= 1 &&
-                       cs + kWave * Frame<T>::VEC - 1 <= g.W - 2;
-    if ((kJoinAlternate && (jt.t & 1)) != (g.flip != 0)) {
-      if (inner) join_task<T, MULTI, NT, NORM, true, NTF, false>(g, jt, tab, rtb, ptb, ssq);
-      else join_task<T, MULTI, NT, NORM, true, NTF, true>(g, jt, tab, rtb, ptb, ssq);
-    } else {
-      if (inner) join_task<T, MULTI, NT, NORM, false, NTF, false>(g, jt, tab, rtb, ptb, ssq);
-      else join_task<T, MULTI, NT, NORM, false, NTF, true>(g, jt, tab, rtb, ptb, ssq);
-    }
+    if (((jt.t & 1) != 0) != (g.flip != 0)) join_task<T, MULTI, NT, NORM, true, NTF>(g, jt, tab, rtb, ptb, ssq);
+    else join_task<T, MULTI, NT, NORM, false, NTF>(g, jt, tab, rtb, ptb, ssq);
   }
   if constexpr (NORM) norm_partial<T>(g, ssq);
 }
@@ -2651,9 +2563,6 @@ static void join_config(int B, int H, int W, MgArgs<T>& g) {
   g.nstrips = div_up(W - 2, Ovl3<T>::S);
   const int rb_pow2 = pick_rb(B, g.nstrips, H - 2, join_max_rb());
   g.rb = B >= kJoinBatchPow2 ? rb_pow2 : balanced_rb(B, g.nstrips, (H + 1) / 2 - 2, 7, rb_pow2, kJoinMinWaves);
-#ifdef FEA_LAB_JOIN_RB  // lab builds: a fixed task height (fine rows, even) for A/B runs
-  g.rb = FEA_LAB_JOIN_RB;
-#endif
   g.ntr = div_up((H + 1) / 2 - 2, g.rb / 2);
 }
 
@@ -2676,290 +2585,264 @@ extern "C" int fea_norm_append(const double* ws, long long stride, long long per
                                unsigned* cnt, void* stream) {
   if (!ws || !hist || !cnt || B <= 0 || nrows <= 0 || per <= 0 || (nrows > 1 && stride < B * per)) return FEA_EINVAL;
   k_norm_append<<<1, 256, 0, (hipStream_t)stream>>>(ws, stride, per, B, nrows, hist, cnt);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
-#define FEA_NT_LAUNCH(K, TARGS)                                   \
-  {                                                               \
-    if (g.nt) K<TARGS, true><<<grid, 256, 0, s>>>(g);             \
-    else K<TARGS, false><<<grid, 256, 0, s>>>(g);                 \
-  }
+// ---------------------------------------------------------------------------
+// Entry points: one function template each (checks, launch geometry, streaming policy, kernel dispatch); the
+// extern "C" symbols at the end of the file only forward to them.  Kernel flags NT / NTL follow g.nt (0 cached,
+// 1 nontemporal stores, 2 also nontemporal loads).
+// ---------------------------------------------------------------------------
+template <typename T>
+static inline void mg_coarse(MgArgs<T>& g, int ldc, long long bsc) {  // the coarse grid of an intergrid launch
+  g.Hc = (g.H + 1) / 2; g.Wc = (g.W + 1) / 2; g.ldc = ldc; g.bsc = bsc;
+}
+template <typename T>
+static inline void mg_coarse2(MgArgs<T>& g, int ldc2, long long bsc2) {  // the grid below it (two-level kernels)
+  g.Hc2 = (g.Hc + 1) / 2; g.Wc2 = (g.Wc + 1) / 2; g.ldc2 = ldc2; g.bsc2 = bsc2;
+}
 
-// three streaming policies (g.nt: 0 cached, 1 nontemporal stores, 2 also nontemporal loads)
-#define FEA_NT3_LAUNCH(K, TARGS)                                  \
-  {                                                               \
-    if (g.nt == 2) K<TARGS, true, true><<<grid, 256, 0, s>>>(g);  \
-    else if (g.nt) K<TARGS, true, false><<<grid, 256, 0, s>>>(g); \
-    else K<TARGS, false, false><<<grid, 256, 0, s>>>(g);          \
-  }
+// what every restriction checks: both right-hand sides, both layouts, the stencil and restriction tables
+template <typename T>
+static inline bool restrict_ok(const T* f, const T* fc, const uint8_t* pid, const T* ktab, int ntab, const T* rtab,
+                               int nrtab, int B, int H, int W, int ld, long long bs, int ldc, long long bsc) {
+  return f && fc && rtab && B > 0 && layout_ok<T>(H, W, ld, bs) && coarse_ok<T>(H, W, ldc, bsc) &&
+         tab_ok(ktab, ntab, pid) && xtab_ok(nrtab, ntab);
+}
 
-#define FEA_NT_LAUNCH_ZU(K, TARGS)                                \
-  {                                                               \
-    if (g.nt) K<TARGS, true, true><<<grid, 256, 0, s>>>(g);       \
-    else K<TARGS, false, true><<<grid, 256, 0, s>>>(g);           \
-  }
+// a block [r0, r1) x [c0, c1) of an Hs x Ws grid that also goes to an agglomeration send buffer
+template <typename T>
+static inline bool send_block(MgArgs<T>& g, T* send, int r0, int r1, int c0, int c1, int Hs, int Ws) {
+  if (r0 < 0 || r1 <= r0 || c0 < 0 || c1 <= c0 || r1 > Hs || c1 > Ws) return false;
+  g.gsend = send; g.gr0 = r0; g.gr1 = r1; g.gc0 = c0; g.gc1 = c1;
+  return true;
+}
 
-#define FEA_MG_API(SUF, T)                                                                                   \
-  extern "C" int fea_mg_pack_##SUF(const T* src, T* dst, const T* geo, long long geo_bs, const T* bc,         \
-                                   long long bc_bs, int B, int H, int W, int ld, long long bs, void* stream) { \
-    if (!dst || B <= 0 || B > 65535 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;                        \
-    k_mg_pack<T><<<dim3(div_up(W, 64), div_up(H, 4), B), 256, 0, (hipStream_t)stream>>>(src, dst, geo, geo_bs, \
-                                                                                       bc, bc_bs, H, W, ld, bs); \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_unpack_##SUF(const T* src, T* dst, int B, int H, int W, int ld, long long bs,         \
-                                     void* stream) {                                                         \
-    if (!src || !dst || B <= 0 || B > 65535 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;                \
-    k_mg_unpack<T><<<dim3(div_up(W, 64), div_up(H, 4), B), 256, 0, (hipStream_t)stream>>>(src, dst, H, W, ld, \
-                                                                                         bs);                \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_sweep_##SUF(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab,         \
-                                    const T* omd, int ntab, int B, int H, int W, int ld, long long bs,         \
-                                    void* stream) {                                                          \
-    if (!f || !out || !ktab || !omd || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;              \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid) || out == u) return FEA_EINVAL;             \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;                   \
-    if (g.nt && (long long)B * bs * (long long)sizeof(T) > nt_load_bytes()) g.nt = 2;                      \
-    const dim3 grid = mg_grid(B, g.ntr, g.nstrips);                                                          \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    const bool multi = ntab > 1;                                                                             \
-    if (!u) {                                                                                                \
-      if (multi) FEA_NT3_LAUNCH(k_mg_sweep, T COMMA true COMMA true)                                          \
-      else FEA_NT3_LAUNCH(k_mg_sweep, T COMMA false COMMA true)                                               \
-    } else {                                                                                                 \
-      if (multi) FEA_NT3_LAUNCH(k_mg_sweep, T COMMA true COMMA false)                                         \
-      else FEA_NT3_LAUNCH(k_mg_sweep, T COMMA false COMMA false)                                              \
-    }                                                                                                        \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_residual_restrict_##SUF(const T* u, const T* f, T* v_out, T* fc, const uint8_t* pid, \
-                                                const T* ktab, const T* omd, int ntab, const T* rtab,          \
-                                                int nrtab, T w0, int B, int H, int W, int ld, long long bs,    \
-                                                int ldc, long long bsc, void* stream) {                        \
-    if (!f || !fc || !ktab || !rtab || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;               \
-    if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;                                                    \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid)) return FEA_EINVAL;                         \
-    if (nrtab != ntab && nrtab != 1) return FEA_EINVAL;                                                      \
-    if (!u && !omd) return FEA_EINVAL;                                                                       \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.f = f; g.out = fc; g.out2 = v_out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;     \
-    g.rtab = rtab; g.nrtab = nrtab; g.w = w0; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2; g.ldc = ldc;            \
-    g.bsc = bsc;                                                                                             \
-    g.ntr = div_up(g.Hc - 2, g.rb / 2);                                                                      \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    const bool multi = ntab > 1;                                                                             \
-    if (multi && nrtab == 1) return FEA_EINVAL;                                                              \
-    if (!u && !v_out) { /* zero guess, v not kept: overlapped strips (k_mg_zero_restrict) */                \
-      g.nstrips = div_up(W - 2, Ovl<T>::S);                                                                  \
-      g.rb = pick_rb(B, g.nstrips, H - 2);                                                                   \
-      g.ntr = div_up(g.Hc - 2, g.rb / 2);                                                                    \
-      const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);                                                    \
-      if (multi) FEA_NT_LAUNCH(k_mg_zero_restrict, T COMMA true)                                             \
-      else FEA_NT_LAUNCH(k_mg_zero_restrict, T COMMA false)                                                  \
-      FEA_LAUNCH_CHECK();                                                                                    \
-    }                                                                                                        \
-    const dim3 grid = mg_grid(B, g.ntr, g.nstrips);                                                          \
-    if (!u) {                                                                                                \
-      if (multi) FEA_NT_LAUNCH(k_mg_resid_restrict, T COMMA true COMMA true)                                 \
-      else FEA_NT_LAUNCH(k_mg_resid_restrict, T COMMA false COMMA true)                                      \
-    } else {                                                                                                 \
-      if (multi) FEA_NT_LAUNCH(k_mg_resid_restrict, T COMMA true COMMA false)                                \
-      else FEA_NT_LAUNCH(k_mg_resid_restrict, T COMMA false COMMA false)                                     \
-    }                                                                                                        \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_zero_restrict_send_##SUF(const T* f, T* fc, const uint8_t* pid, const T* ktab,           \
-                                                 const T* omd, int ntab, const T* rtab, int nrtab, T w0, int B,  \
-                                                 int H, int W, int ld, long long bs, int ldc, long long bsc,     \
-                                                 T* send, int r0, int r1, int c0, int c1, void* stream) {        \
-    if (!f || !fc || !ktab || !rtab || !omd || !send || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL; \
-    if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;                                                    \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid)) return FEA_EINVAL;                         \
-    if (nrtab != ntab && nrtab != 1) return FEA_EINVAL;                                                      \
-    const bool multi = ntab > 1;                                                                             \
-    if (multi && nrtab == 1) return FEA_EINVAL;                                                              \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.f = f; g.out = fc; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;                              \
-    g.rtab = rtab; g.nrtab = nrtab; g.w = w0; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2; g.ldc = ldc;            \
-    g.bsc = bsc;                                                                                             \
-    if (r0 < 0 || r1 <= r0 || c0 < 0 || c1 <= c0 || r1 > g.Hc || c1 > g.Wc) return FEA_EINVAL;               \
-    g.gsend = send; g.gr0 = r0; g.gr1 = r1; g.gc0 = c0; g.gc1 = c1;                                          \
-    g.nstrips = div_up(W - 2, Ovl<T>::S);                                                                    \
-    g.rb = pick_rb(B, g.nstrips, H - 2);                                                                     \
-    g.ntr = div_up(g.Hc - 2, g.rb / 2);                                                                      \
-    const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);                                                      \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    if (multi) FEA_NT_LAUNCH(k_mg_zero_restrict, T COMMA true)                                               \
-    else FEA_NT_LAUNCH(k_mg_zero_restrict, T COMMA false)                                                    \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_sweep_restrict_##SUF(const T* u, const T* f, T* u_out, T* fc, const uint8_t* pid,       \
-                                             const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab,    \
-                                             T w0, int B, int H, int W, int ld, long long bs, int ldc,          \
-                                             long long bsc, double* norm_ws, double* norm_hist,                 \
-                                             unsigned* norm_cnt, void* stream) {                                \
-    if (!u || !f || !u_out || !fc || !ktab || !omd || !rtab || B <= 0 || !layout_ok<T>(H, W, ld, bs) ||       \
-        u_out == u)                                                                                          \
-      return FEA_EINVAL;                                                                                     \
-    const bool norm = norm_hist != nullptr;                                                                  \
-    if (norm && (!norm_ws || !norm_cnt)) return FEA_EINVAL;                                                  \
-    if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;                                                    \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid) || (nrtab != ntab && nrtab != 1))          \
-      return FEA_EINVAL;                                                                                     \
-    if (ntab > 1 && nrtab == 1) return FEA_EINVAL;                                                           \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.f = f; g.out = fc; g.out2 = u_out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;     \
-    g.rtab = rtab; g.nrtab = nrtab; g.w = w0; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2; g.ldc = ldc;            \
-    g.bsc = bsc;                                                                                             \
-    g.nstrips = div_up(W - 2, Ovl<T>::S);  /* overlapped strips */                                           \
-    g.rb = balanced_rb(B, g.nstrips, g.Hc - 2, 3, pick_rb(B, g.nstrips, H - 2, 2 * kRB));                    \
-    g.ntr = div_up(g.Hc - 2, g.rb / 2);                                                                      \
-    g.part = norm_ws;                                                                                        \
-    const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);                                                      \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    if (norm && (long long)grid.x * kWaves * 8 > (long long)fea_norm_workspace_bytes(B, H, W))               \
-      return FEA_EINVAL;                                                                                     \
-    if (ntab > 1) {                                                                                          \
-      if (norm) FEA_NT_LAUNCH(k_mg_sweep_restrict, T COMMA true COMMA true)                                  \
-      else FEA_NT_LAUNCH(k_mg_sweep_restrict, T COMMA true COMMA false)                                      \
-    } else {                                                                                                 \
-      if (norm) FEA_NT_LAUNCH(k_mg_sweep_restrict, T COMMA false COMMA true)                                 \
-      else FEA_NT_LAUNCH(k_mg_sweep_restrict, T COMMA false COMMA false)                                     \
-    }                                                                                                        \
-    if (norm)                                                                                                \
-      k_norm_append<<<1, 256, 0, s>>>(norm_ws, 0, (long long)(grid.x / B) * kWaves, B, 1, norm_hist, norm_cnt); \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  static int mg_prolong_##SUF(const T* u, const T* ec, const T* f, T* out, const uint8_t* pid,               \
-                              const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab,      \
-                              int nptab, T w1, int B, int H, int W, int ld, long long bs, int ldc,           \
-                              long long bsc, void* stream, bool sweep) {                                     \
-    if ((!u && !sweep) || !ec || !out || !ptab || B <= 0 || !layout_ok<T>(H, W, ld, bs) || out == u)         \
-      return FEA_EINVAL;                                                                                     \
-    if (!u && out == f) return FEA_EINVAL;                                                                   \
-    if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;                                                    \
-    if (nptab < 1 || nptab > FEA_MAX_PATTERNS || (nptab > 1 && !pidc)) return FEA_EINVAL;                    \
-    if (sweep && (!f || !ktab || !omd || ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid)))          \
-      return FEA_EINVAL;                                                                                     \
-    const bool multi = nptab > 1 || (sweep && ntab > 1);                                                     \
-    if (multi && ((sweep && (!pid || ntab == 1)) || !pidc || nptab == 1)) return FEA_EINVAL;                 \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.ec = ec; g.f = f; g.out = out; g.pid = pid; g.pidc = pidc; g.ktab = ktab; g.omd = omd;         \
-    g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.w = w1; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2;          \
-    g.ldc = ldc; g.bsc = bsc;                                                                                \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    if (sweep && !u && zu_ovl((long long)B * bs * (long long)sizeof(T))) { /* overlapped strips */           \
-      g.nstrips = div_up(W - 2, Ovl<T>::S);                                                                  \
-      g.rb = pick_rb(B, g.nstrips, H - 2);                                                                   \
-      g.ntr = div_up(H - 2, g.rb);                                                                           \
-      const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);                                                    \
-      if (multi) FEA_NT_LAUNCH(k_mg_prolong_zu_ovl, T COMMA true)                                            \
-      else FEA_NT_LAUNCH(k_mg_prolong_zu_ovl, T COMMA false)                                                 \
-      FEA_LAUNCH_CHECK();                                                                                    \
-    }                                                                                                        \
-    const dim3 grid = mg_grid(B, g.ntr, g.nstrips);                                                          \
-    if (sweep && !u) {                                                                                       \
-      if (multi) FEA_NT_LAUNCH_ZU(k_mg_prolong, T COMMA true COMMA true)                                     \
-      else FEA_NT_LAUNCH_ZU(k_mg_prolong, T COMMA false COMMA true)                                          \
-    } else if (sweep) {                                                                                      \
-      if (multi) FEA_NT_LAUNCH(k_mg_prolong, T COMMA true COMMA true)                                        \
-      else FEA_NT_LAUNCH(k_mg_prolong, T COMMA false COMMA true)                                             \
-    } else {                                                                                                 \
-      if (multi) FEA_NT_LAUNCH(k_mg_prolong, T COMMA true COMMA false)                                       \
-      else FEA_NT_LAUNCH(k_mg_prolong, T COMMA false COMMA false)                                            \
-    }                                                                                                        \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_prolong_sweep_##SUF(const T* u, const T* ec, const T* f, T* out, const uint8_t* pid,  \
-                                            const uint8_t* pidc, const T* ktab, const T* omd, int ntab,       \
-                                            const T* ptab, int nptab, T w1, int B, int H, int W, int ld,     \
-                                            long long bs, int ldc, long long bsc, void* stream) {             \
-    return mg_prolong_##SUF(u, ec, f, out, pid, pidc, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld, bs, ldc, \
-                            bsc, stream, true);                                                              \
-  }                                                                                                          \
-  extern "C" int fea_mg_prolong_add_##SUF(const T* u, const T* ec, T* out, const uint8_t* pidc, const T* ptab, \
-                                          int nptab, T w1, int B, int H, int W, int ld, long long bs, int ldc, \
-                                          long long bsc, void* stream) {                                     \
-    return mg_prolong_##SUF(u, ec, nullptr, out, nullptr, pidc, nullptr, nullptr, 0, ptab, nptab, w1, B, H,  \
-                            W, ld, bs, ldc, bsc, stream, false);                                             \
-  }                                                                                                          \
-  extern "C" int fea_mg_cycle_join_##SUF(const T* u, const T* ec, const T* f, T* u_out, T* fc, const uint8_t* pid, \
-                                         const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab, \
-                                         int nptab, const T* rtab, int nrtab, T w1, T w0, int B, int H, int W,     \
-                                         int ld, long long bs, int ldc, long long bsc, double* norm_ws,          \
-                                         double* norm_hist, unsigned* norm_cnt, void* stream) {                  \
-    if (!u || !ec || !f || !u_out || !fc || !ktab || !omd || !ptab || !rtab || B <= 0 || u_out == u)          \
-      return FEA_EINVAL;                                                                                     \
-    const bool norm = norm_ws != nullptr, append = norm_hist != nullptr;                                      \
-    if (append && (!norm_ws || !norm_cnt)) return FEA_EINVAL;                                                \
-    if (!layout_ok<T>(H, W, ld, bs) || !coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;                     \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (nrtab != ntab && nrtab != 1) || (nptab != ntab && nptab != 1)) \
-      return FEA_EINVAL;                                                                                     \
-    const bool multi = ntab > 1;                                                                             \
-    if (multi && (!pid || !pidc || nrtab == 1 || nptab == 1)) return FEA_EINVAL;                             \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.ec = ec; g.f = f; g.out = fc; g.out2 = u_out; g.pid = pid; g.pidc = pidc; g.ktab = ktab;       \
-    g.omd = omd; g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.rtab = rtab; g.nrtab = nrtab; g.w = w0;     \
-    g.w2 = w1; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2; g.ldc = ldc; g.bsc = bsc;                              \
-    join_config<T>(B, H, W, g);                                                                              \
-    if (g.nt && bs * (long long)sizeof(T) > nt_load_bytes()) g.nt = 2;                                         \
-    FEA_LAB_JOIN_REV(g);                                                                                     \
-    g.part = norm_ws;                                                                                        \
-    const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);                                                      \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    if (norm && (long long)grid.x * kWaves * 8 > (long long)fea_norm_workspace_bytes(B, H, W))               \
-      return FEA_EINVAL;                                                                                     \
-    if (multi) {                                                                                             \
-      if (norm) FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA true COMMA true)                                      \
-      else FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA true COMMA false)                                          \
-    } else {                                                                                                 \
-      if (norm) FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA false COMMA true)                                     \
-      else FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA false COMMA false)                                         \
-    }                                                                                                        \
-    if (append)                                                                                              \
-      k_norm_append<<<1, 256, 0, s>>>(norm_ws, 0, (long long)(grid.x / B) * kWaves, B, 1, norm_hist, norm_cnt); \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_mg_residual_norm_##SUF(const T* u, const T* f, const uint8_t* pid, const T* ktab,        \
-                                            int ntab, double* out, double* ws, int B, int H, int W, int ld,   \
-                                            long long bs, int rlo, int rhi, int clo, int chi, void* stream) {\
-    if (!u || !f || !ktab || !out || !ws || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;         \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid)) return FEA_EINVAL;                         \
-    if (rlo == 0 && rhi == 0) {                                                                              \
-      rlo = 1;                                                                                               \
-      rhi = H - 1;                                                                                           \
-    }                                                                                                        \
-    if (rlo < 1 || rhi > H - 1 || rhi < rlo) return FEA_EINVAL;                                              \
-    if (clo == 0 && chi == 0) {                                                                              \
-      clo = 1;                                                                                               \
-      chi = W - 1;                                                                                           \
-    }                                                                                                        \
-    if (clo < 1 || chi > W - 1 || chi < clo) return FEA_EINVAL;                                              \
-    MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);                                                               \
-    g.u = u; g.f = f; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.part = ws;                                \
-    g.rlo = rlo; g.rhi = rhi; g.clo = clo; g.chi = chi;                                                      \
-    g.rb = 2;                                                                                                \
-    while (g.rb < kRB && (long long)B * g.nstrips * div_up(rhi - rlo, g.rb * 2) >= target_waves()) g.rb *= 2; \
-    g.ntr = std::max(div_up(rhi - rlo, g.rb), 1);                                                            \
-    const dim3 grid = mg_grid(B, g.ntr, g.nstrips);                                                          \
-    hipStream_t s = (hipStream_t)stream;                                                                     \
-    if (rhi == rlo) {                                                                                        \
-      (void)hipMemsetAsync(ws, 0, sizeof(double) * (size_t)B * g.nstrips, s);                                      \
-      g.ntr = 1;                                                                                             \
-    } else if (ntab > 1) {                                                                                   \
-      k_mg_resnorm<T, true><<<grid, 256, 0, s>>>(g);                                                         \
-    } else {                                                                                                 \
-      k_mg_resnorm<T, false><<<grid, 256, 0, s>>>(g);                                                        \
-    }                                                                                                        \
-    k_norm_final<<<B, 256, 0, s>>>(ws, (long long)g.ntr * g.nstrips, out);                                   \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }
+template <typename T>
+static int mg_pack(const T* src, T* dst, const T* geo, long long geo_bs, const T* bc, long long bc_bs, int B, int H,
+                   int W, int ld, long long bs, void* stream) {
+  if (!dst || B <= 0 || B > 65535 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
+  k_mg_pack<T><<<dim3(div_up(W, 64), div_up(H, 4), B), 256, 0, (hipStream_t)stream>>>(src, dst, geo, geo_bs, bc, bc_bs,
+                                                                                     H, W, ld, bs);
+  return launch_status();
+}
 
-#define COMMA ,
-FEA_MG_API(f32, float)
-FEA_MG_API(f64, double)
+template <typename T>
+static int mg_unpack(const T* src, T* dst, int B, int H, int W, int ld, long long bs, void* stream) {
+  if (!src || !dst || B <= 0 || B > 65535 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
+  k_mg_unpack<T><<<dim3(div_up(W, 64), div_up(H, 4), B), 256, 0, (hipStream_t)stream>>>(src, dst, H, W, ld, bs);
+  return launch_status();
+}
+
+template <typename T>
+static int mg_sweep(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab, const T* omd, int ntab, int B,
+                    int H, int W, int ld, long long bs, void* stream) {
+  if (!f || !out || !omd || B <= 0 || !layout_ok<T>(H, W, ld, bs) || !tab_ok(ktab, ntab, pid) || out == u)
+    return FEA_EINVAL;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  if (g.nt && (long long)B * bs * (long long)sizeof(T) > nt_load_bytes()) g.nt = 2;
+  const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
+  hipStream_t s = (hipStream_t)stream;
+  with_flags([&](auto multi, auto zero, auto nt, auto ntl) {
+    if constexpr (nt() || !ntl()) k_mg_sweep<T, multi(), zero(), nt(), ntl()><<<grid, 256, 0, s>>>(g);
+  }, ntab > 1, !u, g.nt != 0, g.nt == 2);
+  return launch_status();
+}
+
+// The zero-guess restriction on overlapped strips (k_mg_zero_restrict): its geometry and launch, for
+// fea_mg_residual_restrict (no u, v not kept) and fea_mg_zero_restrict_send.
+template <typename T>
+static int zero_restrict_launch(MgArgs<T>& g, int B, hipStream_t s) {
+  g.nstrips = div_up(g.W - 2, Ovl<T>::S);
+  g.rb = pick_rb(B, g.nstrips, g.H - 2);
+  g.ntr = div_up(g.Hc - 2, g.rb / 2);
+  const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);
+  with_flags([&](auto multi, auto nt) { k_mg_zero_restrict<T, multi(), nt()><<<grid, 256, 0, s>>>(g); },
+             g.ntab > 1, g.nt != 0);
+  return launch_status();
+}
+
+template <typename T>
+static int mg_residual_restrict(const T* u, const T* f, T* v_out, T* fc, const uint8_t* pid, const T* ktab,
+                                const T* omd, int ntab, const T* rtab, int nrtab, T w0, int B, int H, int W, int ld,
+                                long long bs, int ldc, long long bsc, void* stream) {
+  if (!restrict_ok<T>(f, fc, pid, ktab, ntab, rtab, nrtab, B, H, W, ld, bs, ldc, bsc) || (!u && !omd))
+    return FEA_EINVAL;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.f = f; g.out = fc; g.out2 = v_out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
+  mg_coarse(g, ldc, bsc);
+  hipStream_t s = (hipStream_t)stream;
+  if (!u && !v_out) return zero_restrict_launch(g, B, s);  // zero guess, v not kept
+  g.ntr = div_up(g.Hc - 2, g.rb / 2);
+  const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
+  with_flags([&](auto multi, auto zero, auto nt) {
+    k_mg_resid_restrict<T, multi(), zero(), nt()><<<grid, 256, 0, s>>>(g);
+  }, ntab > 1, !u, g.nt != 0);
+  return launch_status();
+}
+
+template <typename T>
+static int mg_zero_restrict_send(const T* f, T* fc, const uint8_t* pid, const T* ktab, const T* omd, int ntab,
+                                 const T* rtab, int nrtab, T w0, int B, int H, int W, int ld, long long bs, int ldc,
+                                 long long bsc, T* send, int r0, int r1, int c0, int c1, void* stream) {
+  if (!restrict_ok<T>(f, fc, pid, ktab, ntab, rtab, nrtab, B, H, W, ld, bs, ldc, bsc) || !omd || !send)
+    return FEA_EINVAL;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.f = f; g.out = fc; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
+  mg_coarse(g, ldc, bsc);
+  if (!send_block(g, send, r0, r1, c0, c1, g.Hc, g.Wc)) return FEA_EINVAL;
+  return zero_restrict_launch(g, B, (hipStream_t)stream);
+}
+
+template <typename T>
+static int mg_sweep_restrict(const T* u, const T* f, T* u_out, T* fc, const uint8_t* pid, const T* ktab, const T* omd,
+                             int ntab, const T* rtab, int nrtab, T w0, int B, int H, int W, int ld, long long bs,
+                             int ldc, long long bsc, double* norm_ws, double* norm_hist, unsigned* norm_cnt,
+                             void* stream) {
+  if (!restrict_ok<T>(f, fc, pid, ktab, ntab, rtab, nrtab, B, H, W, ld, bs, ldc, bsc) || !u || !u_out || !omd ||
+      u_out == u)
+    return FEA_EINVAL;
+  const bool norm = norm_hist != nullptr;
+  if (norm && (!norm_ws || !norm_cnt)) return FEA_EINVAL;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.f = f; g.out = fc; g.out2 = u_out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
+  mg_coarse(g, ldc, bsc);
+  g.nstrips = div_up(W - 2, Ovl<T>::S);  // overlapped strips
+  g.rb = balanced_rb(B, g.nstrips, g.Hc - 2, 3, pick_rb(B, g.nstrips, H - 2, 2 * kRB));
+  g.ntr = div_up(g.Hc - 2, g.rb / 2);
+  g.part = norm_ws;
+  const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);
+  hipStream_t s = (hipStream_t)stream;
+  if (norm && (long long)grid.x * kWaves * 8 > (long long)fea_norm_workspace_bytes(B, H, W)) return FEA_EINVAL;
+  with_flags([&](auto multi, auto nrm, auto nt) {
+    k_mg_sweep_restrict<T, multi(), nrm(), nt()><<<grid, 256, 0, s>>>(g);
+  }, ntab > 1, norm, g.nt != 0);
+  if (norm)
+    k_norm_append<<<1, 256, 0, s>>>(norm_ws, 0, (long long)(grid.x / B) * kWaves, B, 1, norm_hist, norm_cnt);
+  return launch_status();
+}
+
+// fea_mg_prolong_sweep (sweep: the stencil operands are used) and fea_mg_prolong_add
+template <typename T>
+static int mg_prolong(const T* u, const T* ec, const T* f, T* out, const uint8_t* pid, const uint8_t* pidc,
+                      const T* ktab, const T* omd, int ntab, const T* ptab, int nptab, T w1, int B, int H, int W,
+                      int ld, long long bs, int ldc, long long bsc, void* stream, bool sweep) {
+  if ((!u && !sweep) || !ec || !out || B <= 0 || !layout_ok<T>(H, W, ld, bs) || out == u || (!u && out == f))
+    return FEA_EINVAL;
+  if (!coarse_ok<T>(H, W, ldc, bsc) || !tab_ok(ptab, nptab, pidc)) return FEA_EINVAL;
+  if (sweep && (!f || !omd || !tab_ok(ktab, ntab, pid))) return FEA_EINVAL;
+  // with a sweep both tables are per pattern or neither is (their counts may differ, unlike xtab_ok's rule)
+  if (sweep && (ntab > 1) != (nptab > 1)) return FEA_EINVAL;
+  const bool multi = nptab > 1;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.ec = ec; g.f = f; g.out = out; g.pid = pid; g.pidc = pidc; g.ktab = ktab; g.omd = omd;
+  g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.w = w1;
+  mg_coarse(g, ldc, bsc);
+  hipStream_t s = (hipStream_t)stream;
+  const bool zu = sweep && !u;  // the zero-guess iterate omd * f is recomputed
+  if (zu && zu_ovl((long long)B * bs * (long long)sizeof(T))) {  // overlapped strips
+    g.nstrips = div_up(W - 2, Ovl<T>::S);
+    g.rb = pick_rb(B, g.nstrips, H - 2);
+    g.ntr = div_up(H - 2, g.rb);
+    const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);
+    with_flags([&](auto mu, auto nt) { k_mg_prolong_zu_ovl<T, mu(), nt()><<<grid, 256, 0, s>>>(g); }, multi,
+               g.nt != 0);
+    return launch_status();
+  }
+  const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
+  with_flags([&](auto mu, auto sw, auto nt, auto z) {
+    if constexpr (sw() || !z()) k_mg_prolong<T, mu(), sw(), nt(), z()><<<grid, 256, 0, s>>>(g);
+  }, multi, sweep, g.nt != 0, zu);
+  return launch_status();
+}
+
+// The checks and operands that fea_mg_cycle_join and fea_mg_cycle_join_rects share (false: invalid arguments);
+// the task geometry is each caller's own.
+template <typename T>
+static bool join_args(MgArgs<T>& g, const T* u, const T* ec, const T* f, T* u_out, T* fc, const uint8_t* pid,
+                      const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab, int nptab,
+                      const T* rtab, int nrtab, T w1, T w0, int B, int H, int W, int ld, long long bs, int ldc,
+                      long long bsc) {
+  if (!u || !ec || !f || !u_out || !fc || !omd || !ptab || !rtab || B <= 0 || u_out == u) return false;
+  if (!layout_ok<T>(H, W, ld, bs) || !coarse_ok<T>(H, W, ldc, bsc)) return false;
+  if (!tab_ok(ktab, ntab, pid) || (ntab > 1 && !pidc) || !xtab_ok(nrtab, ntab) || !xtab_ok(nptab, ntab)) return false;
+  g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.ec = ec; g.f = f; g.out = fc; g.out2 = u_out; g.pid = pid; g.pidc = pidc; g.ktab = ktab;
+  g.omd = omd; g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
+  g.w2 = w1;
+  mg_coarse(g, ldc, bsc);
+  if (g.nt && bs * (long long)sizeof(T) > nt_load_bytes()) g.nt = 2;
+  return true;
+}
+
+template <typename T, bool NORM>
+static void join_launch(const MgArgs<T>& g, dim3 grid, hipStream_t s) {
+  with_flags([&](auto multi, auto nt, auto ntl) {
+    if constexpr (nt() || !ntl()) k_mg_cycle_join<T, multi(), NORM, nt(), ntl()><<<grid, 256, 0, s>>>(g);
+  }, g.ntab > 1, g.nt != 0, g.nt == 2);
+}
+
+template <typename T>
+static int mg_cycle_join(const T* u, const T* ec, const T* f, T* u_out, T* fc, const uint8_t* pid, const uint8_t* pidc,
+                         const T* ktab, const T* omd, int ntab, const T* ptab, int nptab, const T* rtab, int nrtab,
+                         T w1, T w0, int B, int H, int W, int ld, long long bs, int ldc, long long bsc,
+                         double* norm_ws, double* norm_hist, unsigned* norm_cnt, void* stream) {
+  MgArgs<T> g;
+  if (!join_args(g, u, ec, f, u_out, fc, pid, pidc, ktab, omd, ntab, ptab, nptab, rtab, nrtab, w1, w0, B, H, W, ld, bs,
+                 ldc, bsc))
+    return FEA_EINVAL;
+  const bool norm = norm_ws != nullptr, append = norm_hist != nullptr;
+  if (append && (!norm_ws || !norm_cnt)) return FEA_EINVAL;
+  join_config<T>(B, H, W, g);
+  g.part = norm_ws;
+  const dim3 grid = mg_grid_lin(B, g.ntr, g.nstrips);
+  hipStream_t s = (hipStream_t)stream;
+  if (norm && (long long)grid.x * kWaves * 8 > (long long)fea_norm_workspace_bytes(B, H, W)) return FEA_EINVAL;
+  if (norm) join_launch<T, true>(g, grid, s);
+  else join_launch<T, false>(g, grid, s);
+  if (append)
+    k_norm_append<<<1, 256, 0, s>>>(norm_ws, 0, (long long)(grid.x / B) * kWaves, B, 1, norm_hist, norm_cnt);
+  return launch_status();
+}
+
+template <typename T>
+static int mg_residual_norm(const T* u, const T* f, const uint8_t* pid, const T* ktab, int ntab, double* out,
+                            double* ws, int B, int H, int W, int ld, long long bs, int rlo, int rhi, int clo, int chi,
+                            void* stream) {
+  if (!u || !f || !out || !ws || B <= 0 || !layout_ok<T>(H, W, ld, bs) || !tab_ok(ktab, ntab, pid)) return FEA_EINVAL;
+  if (rlo == 0 && rhi == 0) {  // (0, 0): the whole interior
+    rlo = 1;
+    rhi = H - 1;
+  }
+  if (rlo < 1 || rhi > H - 1 || rhi < rlo) return FEA_EINVAL;
+  if (clo == 0 && chi == 0) {
+    clo = 1;
+    chi = W - 1;
+  }
+  if (clo < 1 || chi > W - 1 || chi < clo) return FEA_EINVAL;
+  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
+  g.u = u; g.f = f; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.part = ws;
+  g.rlo = rlo; g.rhi = rhi; g.clo = clo; g.chi = chi;
+  g.rb = 2;
+  while (g.rb < kRB && (long long)B * g.nstrips * div_up(rhi - rlo, g.rb * 2) >= target_waves()) g.rb *= 2;
+  g.ntr = std::max(div_up(rhi - rlo, g.rb), 1);
+  const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
+  hipStream_t s = (hipStream_t)stream;
+  if (rhi == rlo) {
+    (void)hipMemsetAsync(ws, 0, sizeof(double) * (size_t)B * g.nstrips, s);
+    g.ntr = 1;
+  } else if (ntab > 1) {
+    k_mg_resnorm<T, true><<<grid, 256, 0, s>>>(g);
+  } else {
+    k_mg_resnorm<T, false><<<grid, 256, 0, s>>>(g);
+  }
+  k_norm_final<<<B, 256, 0, s>>>(ws, (long long)g.ntr * g.nstrips, out);
+  return launch_status();
+}
 
 // The cycle join over up to four rectangles of the grid in ONE launch (a domain-decomposed rank's border strips,
 // whose nodes its halo exchange sends, ahead of the interior that runs while the messages are in flight).
@@ -2971,19 +2854,11 @@ static int cycle_join_rects(const T* u, const T* ec, const T* f, T* u_out, T* fc
                             const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab, int nptab,
                             const T* rtab, int nrtab, T w1, T w0, int B, int H, int W, int ld, long long bs, int ldc,
                             long long bsc, int nrect, const int* rects, void* stream) {
-  if (!u || !ec || !f || !u_out || !fc || !ktab || !omd || !ptab || !rtab || B <= 0 || u_out == u || !rects ||
-      nrect < 1 || nrect > 4)
+  MgArgs<T> g;
+  if (!rects || nrect < 1 || nrect > 4 ||
+      !join_args(g, u, ec, f, u_out, fc, pid, pidc, ktab, omd, ntab, ptab, nptab, rtab, nrtab, w1, w0, B, H, W, ld, bs,
+                 ldc, bsc))
     return FEA_EINVAL;
-  if (!layout_ok<T>(H, W, ld, bs) || !coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;
-  if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (nrtab != ntab && nrtab != 1) || (nptab != ntab && nptab != 1))
-    return FEA_EINVAL;
-  const bool multi = ntab > 1;
-  if (multi && (!pid || !pidc || nrtab == 1 || nptab == 1)) return FEA_EINVAL;
-  MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
-  g.u = u; g.ec = ec; g.f = f; g.out = fc; g.out2 = u_out; g.pid = pid; g.pidc = pidc; g.ktab = ktab;
-  g.omd = omd; g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
-  g.w2 = w1; g.Hc = (H + 1) / 2; g.Wc = (W + 1) / 2; g.ldc = ldc; g.bsc = bsc;
-  if (g.nt && bs * (long long)sizeof(T) > nt_load_bytes()) g.nt = 2;
   g.nrect = nrect;
   for (int r = 0; r < nrect; ++r) {
     const int I0 = rects[4 * r], I1 = rects[4 * r + 1], c0 = rects[4 * r + 2], c1 = rects[4 * r + 3];
@@ -3004,24 +2879,9 @@ static int cycle_join_rects(const T* u, const T* ec, const T* f, T* u_out, T* fc
   g.rt[0] = 0;
   for (int r = 0; r < nrect; ++r) g.rt[r + 1] = g.rt[r] + div_up(g.rI1[r] - g.rI0[r], g.rb / 2) * g.rns[r];
   const dim3 grid((unsigned)(B * div_up(g.rt[nrect], kWaves)));
-  hipStream_t s = (hipStream_t)stream;
-  if (multi) FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA true COMMA false)
-  else FEA_NT3_LAUNCH(k_mg_cycle_join, T COMMA false COMMA false)
-  FEA_LAUNCH_CHECK();
+  join_launch<T, false>(g, grid, (hipStream_t)stream);
+  return launch_status();
 }
-
-#define FEA_JOIN_RECTS_API(SUF, T)                                                                            \
-  extern "C" int fea_mg_cycle_join_rects_##SUF(const T* u, const T* ec, const T* f, T* u_out, T* fc,            \
-                                               const uint8_t* pid, const uint8_t* pidc, const T* ktab,          \
-                                               const T* omd, int ntab, const T* ptab, int nptab, const T* rtab,  \
-                                               int nrtab, T w1, T w0, int B, int H, int W, int ld, long long bs,  \
-                                               int ldc, long long bsc, int nrect, const int* rects,             \
-                                               void* stream) {                                                  \
-    return cycle_join_rects<T>(u, ec, f, u_out, fc, pid, pidc, ktab, omd, ntab, ptab, nptab, rtab, nrtab, w1, w0, \
-                               B, H, W, ld, bs, ldc, bsc, nrect, rects, stream);                               \
-  }
-FEA_JOIN_RECTS_API(f32, float)
-FEA_JOIN_RECTS_API(f64, double)
 
 // Rows per task of k_mg_zero_restrict2 (fine rows, a multiple of 4): the tallest power of two that still
 // gives kZr2Waves waves, at least kZr2MinRb (each task recomputes 3 + 1 rows of the intermediate level).
@@ -3040,16 +2900,12 @@ constexpr int kZr2Waves = FEA_ZR2_WAVES;
 // that keep >= 2048 waves and are at most umax units tall; the power-of-two choice `fallback` when none does.  e.g. the 2049^2 fp64 level-pair
 // prolongation: 662 workgroups of 14 rows (<= 3 per CU) instead of 576 of 16 (a quarter of the CUs ran 3 of the
 // 2.25 average).
-#ifndef FEA_BAL2
-#define FEA_BAL2 1
-#endif
 // the fewest waves a two-level launch may have: 1024 (metric V-cycle 132.5 -> 131.0 us against 2048 — fewer,
 // taller tasks re-stream fewer overlap rows; 3072 / 4096 measured +4 us, 512 / 768 +1.5 us; profiles/r06_ab)
 #ifndef FEA_BAL2_WAVES
 #define FEA_BAL2_WAVES 1024
 #endif
 static int balanced_units(int B, int nstrips, int rows_u, int k, int ovh, int fallback, int umax = 256) {
-#if FEA_BAL2
   const long long ncu = num_cus();
   long long best = -1;
   int bu = fallback;
@@ -3061,36 +2917,26 @@ static int balanced_units(int B, int nstrips, int rows_u, int k, int ovh, int fa
     if (best < 0 || cost < best) best = cost, bu = u;
   }
   return bu;
-#else
-  (void)B; (void)nstrips; (void)rows_u; (void)k; (void)ovh; (void)umax;
-  return fallback;
-#endif
 }
 
-// send: the agglomeration's all-gather send buffer ([B, r1 - r0, c1 - c0]) that also receives f_{l+2}'s block
-// [r0, r1) x [c0, c1) (nullptr: none)
+// sending (fea_mg_zero_restrict2_send): f_{l+2}'s block [r0, r1) x [c0, c1) also goes to `send`, the agglomeration's
+// all-gather send buffer ([B, r1 - r0, c1 - c0])
 template <typename T>
 static int zero_restrict2(const T* f, T* fc, T* fc2, const uint8_t* pid, const uint8_t* pidc, const T* ktab,
                           const T* omd, int ntab, const T* rtab, int nrtab, T w0, int B, int H, int W, int ld,
                           long long bs, int ldc, long long bsc, int ldc2, long long bsc2, void* stream,
-                          T* send = nullptr, int r0 = 0, int r1 = 0, int c0 = 0, int c1 = 0) {
-  if (!f || !fc || !fc2 || !ktab || !omd || !rtab || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
-  if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;
-  const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
-  if (!coarse_ok<T>(Hc, Wc, ldc2, bsc2)) return FEA_EINVAL;
+                          bool sending = false, T* send = nullptr, int r0 = 0, int r1 = 0, int c0 = 0, int c1 = 0) {
+  if (!restrict_ok<T>(f, fc, pid, ktab, ntab, rtab, nrtab, B, H, W, ld, bs, ldc, bsc) || !fc2 || !omd ||
+      (sending && !send))
+    return FEA_EINVAL;
+  if (!coarse_ok<T>((H + 1) / 2, (W + 1) / 2, ldc2, bsc2) || (ntab > 1 && !pidc)) return FEA_EINVAL;
   const bool multi = ntab > 1;
-  if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (multi && (!pid || !pidc))) return FEA_EINVAL;
-  if (nrtab != ntab && nrtab != 1) return FEA_EINVAL;
-  if (multi && nrtab == 1) return FEA_EINVAL;
   MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
   g.f = f; g.out = fc; g.out2 = fc2; g.pid = pid; g.pidc = pidc; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
   g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
-  g.Hc = Hc; g.Wc = Wc; g.ldc = ldc; g.bsc = bsc;
-  g.Hc2 = (Hc + 1) / 2; g.Wc2 = (Wc + 1) / 2; g.ldc2 = ldc2; g.bsc2 = bsc2;
-  if (send) {
-    if (r0 < 0 || r1 <= r0 || c0 < 0 || c1 <= c0 || r1 > g.Hc2 || c1 > g.Wc2) return FEA_EINVAL;
-    g.gsend = send; g.gr0 = r0; g.gr1 = r1; g.gc0 = c0; g.gc1 = c1;
-  }
+  mg_coarse(g, ldc, bsc);
+  mg_coarse2(g, ldc2, bsc2);
+  if (send && !send_block(g, send, r0, r1, c0, c1, g.Hc2, g.Wc2)) return FEA_EINVAL;
   g.nstrips = div_up(W - 2, Ovl2<T>::S);
   g.rb = 2 * kRB;
   while (g.rb > kZr2MinRb && (long long)B * g.nstrips * div_up(g.Hc2 - 2, g.rb / 4) < kZr2Waves) g.rb /= 2;
@@ -3100,46 +2946,23 @@ static int zero_restrict2(const T* f, T* fc, T* fc2, const uint8_t* pid, const u
   hipStream_t s = (hipStream_t)stream;
   if (multi) k_mg_zero_restrict2<T, true><<<grid, 256, 0, s>>>(g);
   else k_mg_zero_restrict2<T, false><<<grid, 256, 0, s>>>(g);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
-
-#define FEA_ZR2_API(SUF, T)                                                                                   \
-  extern "C" int fea_mg_zero_restrict2_##SUF(const T* f, T* fc, T* fc2, const uint8_t* pid, const uint8_t* pidc, \
-                                             const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab,     \
-                                             T w0, int B, int H, int W, int ld, long long bs, int ldc,          \
-                                             long long bsc, int ldc2, long long bsc2, void* stream) {            \
-    return zero_restrict2<T>(f, fc, fc2, pid, pidc, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc,  \
-                             ldc2, bsc2, stream);                                                              \
-  }                                                                                                           \
-  extern "C" int fea_mg_zero_restrict2_send_##SUF(const T* f, T* fc, T* fc2, const uint8_t* pid,                \
-                                                  const uint8_t* pidc, const T* ktab, const T* omd, int ntab,    \
-                                                  const T* rtab, int nrtab, T w0, int B, int H, int W, int ld,   \
-                                                  long long bs, int ldc, long long bsc, int ldc2, long long bsc2, \
-                                                  T* send, int r0, int r1, int c0, int c1, void* stream) {       \
-    if (!send) return FEA_EINVAL;                                                                             \
-    return zero_restrict2<T>(f, fc, fc2, pid, pidc, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc,  \
-                             ldc2, bsc2, stream, send, r0, r1, c0, c1);                                        \
-  }
-FEA_ZR2_API(f32, float)
-FEA_ZR2_API(f64, double)
 
 template <typename T>
 static int prolong2(const T* fc, const T* ec2, const T* f, T* out, const uint8_t* pid, const uint8_t* pidc,
                     const uint8_t* pidc2, const T* ktab, const T* omd, int ntab, const T* ptab, int nptab, T w1, int B,
                     int H, int W, int ld, long long bs, int ldc, long long bsc, int ldc2, long long bsc2,
                     void* stream) {
-  if (!fc || !ec2 || !f || !out || !ktab || !omd || !ptab || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
-  if (!coarse_ok<T>(H, W, ldc, bsc)) return FEA_EINVAL;
-  const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
-  if (!coarse_ok<T>(Hc, Wc, ldc2, bsc2)) return FEA_EINVAL;
+  if (!fc || !ec2 || !f || !out || !omd || !ptab || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
+  if (!coarse_ok<T>(H, W, ldc, bsc) || !coarse_ok<T>((H + 1) / 2, (W + 1) / 2, ldc2, bsc2)) return FEA_EINVAL;
   const bool multi = ntab > 1;
-  if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (nptab != ntab && nptab != 1)) return FEA_EINVAL;
-  if (multi && (!pid || !pidc || !pidc2 || nptab == 1)) return FEA_EINVAL;
+  if (!tab_ok(ktab, ntab, pid) || (multi && (!pidc || !pidc2)) || !xtab_ok(nptab, ntab)) return FEA_EINVAL;
   MgArgs<T> g = mg_args<T>(H, W, ld, bs, B);
   g.ec = fc; g.ec2 = ec2; g.f = f; g.out = out; g.pid = pid; g.pidc = pidc; g.pidc2 = pidc2; g.ktab = ktab;
   g.omd = omd; g.ntab = ntab; g.ptab = ptab; g.nptab = nptab; g.w = w1;
-  g.Hc = Hc; g.Wc = Wc; g.ldc = ldc; g.bsc = bsc;
-  g.Hc2 = (Hc + 1) / 2; g.Wc2 = (Wc + 1) / 2; g.ldc2 = ldc2; g.bsc2 = bsc2;
+  mg_coarse(g, ldc, bsc);
+  mg_coarse2(g, ldc2, bsc2);
   g.nstrips = div_up(W - 2, Ovl4<T>::S);
   // (no taller tasks than the power-of-two choice: batched fp32 prolong2 at 1025^2 x 256 ran 41.7 -> 51.5 us with
   // half the waves)
@@ -3150,17 +2973,99 @@ static int prolong2(const T* fc, const T* ec2, const T* f, T* out, const uint8_t
   hipStream_t s = (hipStream_t)stream;
   if (multi) k_mg_prolong2<T, true><<<grid, 256, 0, s>>>(g);
   else k_mg_prolong2<T, false><<<grid, 256, 0, s>>>(g);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
-#define FEA_PROLONG2_API(SUF, T)                                                                              \
-  extern "C" int fea_mg_prolong2_##SUF(const T* fc, const T* ec2, const T* f, T* out, const uint8_t* pid,      \
-                                       const uint8_t* pidc, const uint8_t* pidc2, const T* ktab, const T* omd,  \
-                                       int ntab, const T* ptab, int nptab, T w1, int B, int H, int W, int ld,   \
-                                       long long bs, int ldc, long long bsc, int ldc2, long long bsc2,          \
-                                       void* stream) {                                                        \
-    return prolong2<T>(fc, ec2, f, out, pid, pidc, pidc2, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld, bs, ldc, \
-                       bsc, ldc2, bsc2, stream);                                                               \
+// The exported symbols: each only forwards to its template.
+#define FEA_MG_API(SUF, T)                                                                                           \
+  extern "C" int fea_mg_pack_##SUF(const T* src, T* dst, const T* geo, long long geo_bs, const T* bc, long long bc_bs, \
+                                   int B, int H, int W, int ld, long long bs, void* stream) {                         \
+    return mg_pack<T>(src, dst, geo, geo_bs, bc, bc_bs, B, H, W, ld, bs, stream);                                     \
+  }                                                                                                                  \
+  extern "C" int fea_mg_unpack_##SUF(const T* src, T* dst, int B, int H, int W, int ld, long long bs, void* stream) { \
+    return mg_unpack<T>(src, dst, B, H, W, ld, bs, stream);                                                          \
+  }                                                                                                                  \
+  extern "C" int fea_mg_sweep_##SUF(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab, const T* omd,   \
+                                    int ntab, int B, int H, int W, int ld, long long bs, void* stream) {              \
+    return mg_sweep<T>(u, f, out, pid, ktab, omd, ntab, B, H, W, ld, bs, stream);                                    \
+  }                                                                                                                  \
+  extern "C" int fea_mg_residual_restrict_##SUF(const T* u, const T* f, T* v_out, T* fc, const uint8_t* pid,          \
+                                                const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab,      \
+                                                T w0, int B, int H, int W, int ld, long long bs, int ldc,            \
+                                                long long bsc, void* stream) {                                       \
+    return mg_residual_restrict<T>(u, f, v_out, fc, pid, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc,  \
+                                   stream);                                                                          \
+  }                                                                                                                  \
+  extern "C" int fea_mg_zero_restrict_send_##SUF(const T* f, T* fc, const uint8_t* pid, const T* ktab, const T* omd,   \
+                                                 int ntab, const T* rtab, int nrtab, T w0, int B, int H, int W,       \
+                                                 int ld, long long bs, int ldc, long long bsc, T* send, int r0,       \
+                                                 int r1, int c0, int c1, void* stream) {                             \
+    return mg_zero_restrict_send<T>(f, fc, pid, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc, send, r0,  \
+                                    r1, c0, c1, stream);                                                             \
+  }                                                                                                                  \
+  extern "C" int fea_mg_zero_restrict2_##SUF(const T* f, T* fc, T* fc2, const uint8_t* pid, const uint8_t* pidc,      \
+                                             const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab, T w0,   \
+                                             int B, int H, int W, int ld, long long bs, int ldc, long long bsc,      \
+                                             int ldc2, long long bsc2, void* stream) {                               \
+    return zero_restrict2<T>(f, fc, fc2, pid, pidc, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc, ldc2, \
+                             bsc2, stream);                                                                          \
+  }                                                                                                                  \
+  extern "C" int fea_mg_zero_restrict2_send_##SUF(const T* f, T* fc, T* fc2, const uint8_t* pid, const uint8_t* pidc, \
+                                                  const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab,    \
+                                                  T w0, int B, int H, int W, int ld, long long bs, int ldc,          \
+                                                  long long bsc, int ldc2, long long bsc2, T* send, int r0, int r1,   \
+                                                  int c0, int c1, void* stream) {                                    \
+    return zero_restrict2<T>(f, fc, fc2, pid, pidc, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc, ldc2, \
+                             bsc2, stream, true, send, r0, r1, c0, c1);                                              \
+  }                                                                                                                  \
+  extern "C" int fea_mg_sweep_restrict_##SUF(const T* u, const T* f, T* u_out, T* fc, const uint8_t* pid,             \
+                                             const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab, T w0,   \
+                                             int B, int H, int W, int ld, long long bs, int ldc, long long bsc,      \
+                                             double* norm_ws, double* norm_hist, unsigned* norm_cnt, void* stream) {  \
+    return mg_sweep_restrict<T>(u, f, u_out, fc, pid, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld, bs, ldc, bsc,     \
+                                norm_ws, norm_hist, norm_cnt, stream);                                               \
+  }                                                                                                                  \
+  extern "C" int fea_mg_prolong_sweep_##SUF(const T* u, const T* ec, const T* f, T* out, const uint8_t* pid,          \
+                                            const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab, \
+                                            int nptab, T w1, int B, int H, int W, int ld, long long bs, int ldc,      \
+                                            long long bsc, void* stream) {                                           \
+    return mg_prolong<T>(u, ec, f, out, pid, pidc, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld, bs, ldc, bsc, stream, \
+                         true);                                                                                      \
+  }                                                                                                                  \
+  extern "C" int fea_mg_prolong_add_##SUF(const T* u, const T* ec, T* out, const uint8_t* pidc, const T* ptab,        \
+                                          int nptab, T w1, int B, int H, int W, int ld, long long bs, int ldc,        \
+                                          long long bsc, void* stream) {                                             \
+    return mg_prolong<T>(u, ec, nullptr, out, nullptr, pidc, nullptr, nullptr, 0, ptab, nptab, w1, B, H, W, ld, bs,   \
+                         ldc, bsc, stream, false);                                                                   \
+  }                                                                                                                  \
+  extern "C" int fea_mg_prolong2_##SUF(const T* fc, const T* ec2, const T* f, T* out, const uint8_t* pid,             \
+                                       const uint8_t* pidc, const uint8_t* pidc2, const T* ktab, const T* omd,        \
+                                       int ntab, const T* ptab, int nptab, T w1, int B, int H, int W, int ld,        \
+                                       long long bs, int ldc, long long bsc, int ldc2, long long bsc2,               \
+                                       void* stream) {                                                               \
+    return prolong2<T>(fc, ec2, f, out, pid, pidc, pidc2, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld, bs, ldc, bsc, \
+                       ldc2, bsc2, stream);                                                                          \
+  }                                                                                                                  \
+  extern "C" int fea_mg_cycle_join_##SUF(const T* u, const T* ec, const T* f, T* u_out, T* fc, const uint8_t* pid,    \
+                                         const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* ptab,   \
+                                         int nptab, const T* rtab, int nrtab, T w1, T w0, int B, int H, int W,        \
+                                         int ld, long long bs, int ldc, long long bsc, double* norm_ws,              \
+                                         double* norm_hist, unsigned* norm_cnt, void* stream) {                      \
+    return mg_cycle_join<T>(u, ec, f, u_out, fc, pid, pidc, ktab, omd, ntab, ptab, nptab, rtab, nrtab, w1, w0, B, H,  \
+                            W, ld, bs, ldc, bsc, norm_ws, norm_hist, norm_cnt, stream);                              \
+  }                                                                                                                  \
+  extern "C" int fea_mg_cycle_join_rects_##SUF(const T* u, const T* ec, const T* f, T* u_out, T* fc,                  \
+                                               const uint8_t* pid, const uint8_t* pidc, const T* ktab, const T* omd,  \
+                                               int ntab, const T* ptab, int nptab, const T* rtab, int nrtab, T w1,    \
+                                               T w0, int B, int H, int W, int ld, long long bs, int ldc,             \
+                                               long long bsc, int nrect, const int* rects, void* stream) {           \
+    return cycle_join_rects<T>(u, ec, f, u_out, fc, pid, pidc, ktab, omd, ntab, ptab, nptab, rtab, nrtab, w1, w0, B,  \
+                               H, W, ld, bs, ldc, bsc, nrect, rects, stream);                                        \
+  }                                                                                                                  \
+  extern "C" int fea_mg_residual_norm_##SUF(const T* u, const T* f, const uint8_t* pid, const T* ktab, int ntab,      \
+                                            double* out, double* ws, int B, int H, int W, int ld, long long bs,      \
+                                            int rlo, int rhi, int clo, int chi, void* stream) {                      \
+    return mg_residual_norm<T>(u, f, pid, ktab, ntab, out, ws, B, H, W, ld, bs, rlo, rhi, clo, chi, stream);          \
   }
-FEA_PROLONG2_API(f32, float)
-FEA_PROLONG2_API(f64, double)
+FEA_MG_API(f32, float)
+FEA_MG_API(f64, double)

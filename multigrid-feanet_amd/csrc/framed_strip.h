@@ -30,13 +30,9 @@ template <typename T>
 __device__ __forceinline__ T tabv(const T* t, int off, int d) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(t) + off + d * (int)sizeof(T));
 }
-// The restricted field f_c (a quarter of the level's bytes) is stored with normal stores even when
-// the level's own stores stream past the caches: the next kernel (the coarse level's restriction)
+// The restricted field f_c (a quarter of the level's bytes) is stored with normal stores (vstore<T, Q>) even
+// when the level's own stores stream past the caches: the next kernel (the coarse level's restriction)
 // reads it straight back, from the Infinity Cache instead of HBM.
-#ifndef FEA_COARSE_NT
-#define FEA_COARSE_NT 0
-#endif
-constexpr bool kCoarseNT = FEA_COARSE_NT != 0;
 
 static inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
@@ -197,16 +193,13 @@ __device__ __forceinline__ PRow<V> finish_p(const RawP<V>& r) {
 // CENTRE's pattern (stencil_table(); MultigridSolver checks it on every level's map, mesh_setup
 // .stencil_mirror_mismatches).  All nine weights then come from one table row — one base address, adjacent
 // offsets — instead of three rows picked by the window's neighbour patterns; taps are summed in the same order, so
-// every value is the same bits as before.
-#ifndef FEA_KSYM
-#define FEA_KSYM 1
-#endif
+// every value is the same bits as with the neighbours' rows.
 template <typename T, int V, bool MULTI>
 __device__ __forceinline__ T kapply(const Row<T, V>& w0, const Row<T, V>& w1, const Row<T, V>& w2,
                                     const PRow<V>& p0, const PRow<V>& p1, const PRow<V>& p2, int k,
                                     const T (&ks)[9], const T* tab) {
   T acc;
-  if constexpr (MULTI && FEA_KSYM) {
+  if constexpr (MULTI) {
     const int pc = p1.a[k + 1];
     acc = tabv(tab, pc, 8) * w0.a[k];
     acc += tabv(tab, pc, 7) * w0.a[k + 1];
@@ -217,7 +210,7 @@ __device__ __forceinline__ T kapply(const Row<T, V>& w0, const Row<T, V>& w1, co
     acc += tabv(tab, pc, 2) * w2.a[k];
     acc += tabv(tab, pc, 1) * w2.a[k + 1];
     acc += tabv(tab, pc, 0) * w2.a[k + 2];
-  } else if constexpr (!MULTI) {
+  } else {
     acc = ks[0] * w0.a[k];
     acc += ks[1] * w0.a[k + 1];
     acc += ks[2] * w0.a[k + 2];
@@ -227,16 +220,6 @@ __device__ __forceinline__ T kapply(const Row<T, V>& w0, const Row<T, V>& w1, co
     acc += ks[6] * w2.a[k];
     acc += ks[7] * w2.a[k + 1];
     acc += ks[8] * w2.a[k + 2];
-  } else {
-    acc = tabv(tab, p0.a[k], 0) * w0.a[k];
-    acc += tabv(tab, p0.a[k + 1], 1) * w0.a[k + 1];
-    acc += tabv(tab, p0.a[k + 2], 2) * w0.a[k + 2];
-    acc += tabv(tab, p1.a[k], 3) * w1.a[k];
-    acc += tabv(tab, p1.a[k + 1], 4) * w1.a[k + 1];
-    acc += tabv(tab, p1.a[k + 2], 5) * w1.a[k + 2];
-    acc += tabv(tab, p2.a[k], 6) * w2.a[k];
-    acc += tabv(tab, p2.a[k + 1], 7) * w2.a[k + 1];
-    acc += tabv(tab, p2.a[k + 2], 8) * w2.a[k + 2];
   }
   return acc;
 }
@@ -273,6 +256,7 @@ struct MgArgs {
   int nt;            // 1: nontemporal stores (level larger than FEANET_NT_BYTES); 2: also loads (sweep, join)
   int rev;           // decode_task_lin: deal the launch's tasks in reverse order (last task first)
   int flip;          // cycle join: every task streams in the other direction (even tasks bottom-up, odd top-down)
+  // (rev and flip are always 0 — nothing sets them any more; the kernels read them, so dropping them changes device code)
   // cycle join over up to 4 rectangles (nrect > 0; a domain-decomposed rank's border strips, then its interior):
   // rectangle r = coarse rows [rI0[r], rI1[r]) x fine columns [rc0[r], rc1[r]) (odd bounds, coarse column J owned
   // with its fine columns 2J-1, 2J), its nstrips rns[r], its row tasks rnt[r]; the launch's tasks per sample are

@@ -523,146 +523,218 @@ using namespace fea;
 static inline dim3 grid_for(int H, int W, int B) { return dim3((W + kBX - 1) / kBX, (H + kBY - 1) / kBY, B); }
 static inline bool bad_shape(int B, int H, int W) { return B <= 0 || H <= 0 || W <= 0 || B > 65535; }
 
-#define FEA_GENERIC_API(SUF, T)                                                                          \
-  extern "C" int fea_knet_apply_##SUF(const T* u, T* y, const uint8_t* pid, const T* ktab, int ntab, int B, \
-                                      int H, int W, void* stream) {                                      \
-    if (!u || !y || !ktab || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W)) return FEA_EINVAL; \
-    k_knet<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, y, pid, ktab, ntab, H, W); \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_split_x_##SUF(const T* x, T* xs, const uint8_t* pid, int C, int B, int H, int W,   \
-                                   void* stream) {                                                       \
-    if (!x || !xs || C < 1 || bad_shape(B, H, W)) return FEA_EINVAL;                                     \
-    k_split<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(x, xs, pid, C, H, W);       \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_jacobi_sweep_##SUF(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab, \
-                                        const T* omd, int ntab, const T* geo, long long geo_bs,          \
-                                        const T* bc, long long bc_bs, int B, int H, int W, void* stream) { \
-    if (!u || !f || !out || !ktab || !omd || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W))  \
-      return FEA_EINVAL;                                                                                 \
-    if (out == u) return FEA_EINVAL;                                                                     \
-    k_jacobi<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, f, out, pid, ktab, omd, \
-                                                                                ntab, geo, geo_bs, bc,   \
-                                                                                bc_bs, H, W);            \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_jacobi_sweep_pbc_##SUF(const T* u, const T* f, T* out, const T* ktab, const T* omd,  \
-                                            int B, int N, void* stream) {                                \
-    if (!u || !f || !out || !ktab || !omd || out == u || bad_shape(B, N, N)) return FEA_EINVAL;          \
-    k_jacobi_pbc<T><<<grid_for(N, N, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, f, out, ktab, omd, N); \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_pbc_pad_##SUF(const T* u, T* dst, int B, int N, int lo, int hi, void* stream) {     \
-    if (!u || !dst || lo < 0 || hi < 0 || lo + hi > 64 || bad_shape(B, N, N)) return FEA_EINVAL;         \
-    const int M = N - 1 + lo + hi;                                                                       \
-    k_pbc_pad<T><<<grid_for(M, M, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, dst, N, lo, M);        \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_residual_##SUF(const T* u, const T* f, T* r, const uint8_t* pid, const T* ktab,    \
-                                    int ntab, int B, int H, int W, void* stream) {                       \
-    if (!u || !f || !r || !ktab || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W))            \
-      return FEA_EINVAL;                                                                                 \
-    k_residual<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, f, r, pid, ktab, ntab, \
-                                                                                  H, W);                 \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_restrict_##SUF(const T* x, int C, T* fc, const uint8_t* pid, const T* rtab, int ntab, \
-                                    T w0, int B, int H, int W, void* stream) {                           \
-    if (!x || !fc || !rtab || C < 1 || bad_shape(B, H, W) || H < 3 || W < 3 || !(H & 1) || !(W & 1))      \
-      return FEA_EINVAL;                                                                                 \
-    if ((C == 1 && (ntab < 1 || ntab > FEA_MAX_PATTERNS)) || (C > 1 && (ntab != C || C > FEA_MAX_PATTERNS))) \
-      return FEA_EINVAL;                                                                                 \
-    const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;                                                        \
-    k_restrict<T><<<grid_for(Hc, Wc, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(x, C, fc, pid, rtab,  \
-                                                                                    ntab, w0, H, W);     \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_prolong_##SUF(const T* e, int C, T* out, const T* add, const uint8_t* pidc,          \
-                                   const T* ptab, int ntab, T w1, int B, int Hc, int Wc, void* stream) { \
-    if (!e || !out || !ptab || C < 1 || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2) return FEA_EINVAL;     \
-    if ((C == 1 && (ntab < 1 || ntab > FEA_MAX_PATTERNS)) || (C > 1 && (ntab != C || C > FEA_MAX_PATTERNS))) \
-      return FEA_EINVAL;                                                                                 \
-    k_prolong<T><<<grid_for(2 * Hc - 1, 2 * Wc - 1, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(       \
-        e, C, out, add, pidc, ptab, ntab, w1, Hc, Wc);                                                   \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_residual_norm_##SUF(const T* u, const T* f, const uint8_t* pid, const T* ktab,     \
-                                         int ntab, double* out, double* ws, int B, int H, int W,         \
-                                         void* stream) {                                                 \
-    if (!u || !out || !ws || bad_shape(B, H, W) || H < 3 || W < 3) return FEA_EINVAL;                     \
-    if (f && (!ktab || ntab < 1 || ntab > FEA_MAX_PATTERNS)) return FEA_EINVAL;                           \
-    const dim3 g = grid_for(H, W, B);                                                                    \
-    k_norm_partial<T><<<g, dim3(kBX, kBY), 0, (hipStream_t)stream>>>(u, f, pid, f ? ktab : nullptr, ntab, \
-                                                                      ws, H, W);                         \
-    k_norm_final<<<B, 256, 0, (hipStream_t)stream>>>(ws, (long long)g.x * g.y, out);                  \
-    FEA_LAUNCH_CHECK();                                                                                  \
+static inline bool ntab_ok(int ntab) { return ntab >= 1 && ntab <= FEA_MAX_PATTERNS; }  // (pid may be NULL: pattern 0)
+// transfer tables on a field split into C material channels: one table row per channel (one channel: any count)
+static inline bool split_ok(int C, int ntab) { return C == 1 ? ntab_ok(ntab) : C > 1 && ntab == C && ntab_ok(C); }
+static inline bool odd_grid(int H, int W) { return H >= 3 && W >= 3 && (H & 1) && (W & 1); }
+static inline size_t grad_ws_bytes(int n, int B, int H, int W) {  // one partial per block and table entry
+  const dim3 gr = grid_for(H, W, B);
+  return (size_t)n * 9 * gr.x * gr.y * gr.z * sizeof(double);
+}
+static const dim3 kBlock(kBX, kBY);
+
+template <typename T>
+static int knet_apply(const T* u, T* y, const uint8_t* pid, const T* ktab, int ntab, int B, int H, int W, void* stream) {
+  if (!u || !y || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W)) return FEA_EINVAL;
+  k_knet<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(u, y, pid, ktab, ntab, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int split_x(const T* x, T* xs, const uint8_t* pid, int C, int B, int H, int W, void* stream) {
+  if (!x || !xs || C < 1 || bad_shape(B, H, W)) return FEA_EINVAL;
+  k_split<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(x, xs, pid, C, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int jacobi_sweep(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab, const T* omd, int ntab,
+                        const T* geo, long long geo_bs, const T* bc, long long bc_bs, int B, int H, int W,
+                        void* stream) {
+  if (!u || !f || !out || !ktab || !omd || !ntab_ok(ntab) || bad_shape(B, H, W) || out == u) return FEA_EINVAL;
+  k_jacobi<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(u, f, out, pid, ktab, omd, ntab, geo, geo_bs, bc,
+                                                                    bc_bs, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int jacobi_sweep_pbc(const T* u, const T* f, T* out, const T* ktab, const T* omd, int B, int N, void* stream) {
+  if (!u || !f || !out || !ktab || !omd || out == u || bad_shape(B, N, N)) return FEA_EINVAL;
+  k_jacobi_pbc<T><<<grid_for(N, N, B), kBlock, 0, (hipStream_t)stream>>>(u, f, out, ktab, omd, N);
+  return launch_status();
+}
+
+template <typename T>
+static int pbc_pad(const T* u, T* dst, int B, int N, int lo, int hi, void* stream) {
+  if (!u || !dst || lo < 0 || hi < 0 || lo + hi > 64 || bad_shape(B, N, N)) return FEA_EINVAL;
+  const int M = N - 1 + lo + hi;
+  k_pbc_pad<T><<<grid_for(M, M, B), kBlock, 0, (hipStream_t)stream>>>(u, dst, N, lo, M);
+  return launch_status();
+}
+
+template <typename T>
+static int residual(const T* u, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab, int B, int H, int W,
+                    void* stream) {
+  if (!u || !f || !r || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W)) return FEA_EINVAL;
+  k_residual<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(u, f, r, pid, ktab, ntab, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int restrict_(const T* x, int C, T* fc, const uint8_t* pid, const T* rtab, int ntab, T w0, int B, int H, int W,
+                     void* stream) {
+  if (!x || !fc || !rtab || bad_shape(B, H, W) || !odd_grid(H, W) || !split_ok(C, ntab)) return FEA_EINVAL;
+  k_restrict<T><<<grid_for((H + 1) / 2, (W + 1) / 2, B), kBlock, 0, (hipStream_t)stream>>>(x, C, fc, pid, rtab, ntab,
+                                                                                          w0, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int prolong(const T* e, int C, T* out, const T* add, const uint8_t* pidc, const T* ptab, int ntab, T w1, int B,
+                   int Hc, int Wc, void* stream) {
+  if (!e || !out || !ptab || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2 || !split_ok(C, ntab)) return FEA_EINVAL;
+  k_prolong<T><<<grid_for(2 * Hc - 1, 2 * Wc - 1, B), kBlock, 0, (hipStream_t)stream>>>(e, C, out, add, pidc, ptab, ntab,
+                                                                                       w1, Hc, Wc);
+  return launch_status();
+}
+
+template <typename T>
+static int residual_norm(const T* u, const T* f, const uint8_t* pid, const T* ktab, int ntab, double* out, double* ws,
+                         int B, int H, int W, void* stream) {
+  if (!u || !out || !ws || bad_shape(B, H, W) || H < 3 || W < 3) return FEA_EINVAL;
+  if (f && (!ktab || !ntab_ok(ntab))) return FEA_EINVAL;  // (no f: the norm of u itself)
+  const dim3 g = grid_for(H, W, B);
+  k_norm_partial<T><<<g, kBlock, 0, (hipStream_t)stream>>>(u, f, pid, f ? ktab : nullptr, ntab, ws, H, W);
+  k_norm_final<<<B, 256, 0, (hipStream_t)stream>>>(ws, (long long)g.x * g.y, out);
+  return launch_status();
+}
+
+// adjoints (autograd)
+template <typename T>
+static int knet_apply_adj(const T* g, T* out, const uint8_t* pid, const T* ktab, int ntab, int B, int H, int W,
+                          void* stream) {
+  if (!g || !out || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W) || g == out) return FEA_EINVAL;
+  k_knet_adj<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(g, out, pid, ktab, ntab, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int jacobi_sweep_adj(const T* g, T* gu, T* gf, const uint8_t* pid, const T* ktab, const T* omd, int ntab,
+                            const T* geo, long long geo_bs, int B, int H, int W, void* stream) {
+  if (!g || !gu || !ktab || !omd || !ntab_ok(ntab) || bad_shape(B, H, W) || g == gu || g == gf) return FEA_EINVAL;
+  k_jacobi_adj<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(g, gu, gf, pid, ktab, omd, ntab, geo, geo_bs,
+                                                                        H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int restrict_adj(const T* g, int C, T* gx, const uint8_t* pid, const T* rtab, int ntab, T w0, int B, int H,
+                        int W, void* stream) {
+  if (!g || !gx || !rtab || bad_shape(B, H, W) || !odd_grid(H, W) || !split_ok(C, ntab)) return FEA_EINVAL;
+  k_restrict_adj<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(g, C, gx, pid, rtab, ntab, w0, H, W);
+  return launch_status();
+}
+
+template <typename T>
+static int prolong_adj(const T* g, int C, T* ge, const uint8_t* pidc, const T* ptab, int ntab, T w1, int B, int Hc,
+                       int Wc, void* stream) {
+  if (!g || !ge || !ptab || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2 || !split_ok(C, ntab)) return FEA_EINVAL;
+  k_prolong_adj<T><<<grid_for(Hc, Wc, B), kBlock, 0, (hipStream_t)stream>>>(g, C, ge, pidc, ptab, ntab, w1, Hc, Wc);
+  return launch_status();
+}
+
+template <typename T>
+static int transfer_weight_grad(const T* cf, int c_split, const T* ff, int f_split, int C, int interior, T scale,
+                                T* gw, double* ws, int B, int Hc, int Wc, void* stream) {
+  if (!cf || !ff || !gw || !ws || !ntab_ok(C) || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2) return FEA_EINVAL;
+  const dim3 gr = grid_for(Hc, Wc, B);
+  k_tapgrad_partial<T><<<gr, kBlock, 0, (hipStream_t)stream>>>(cf, c_split, ff, f_split, C, interior ? 1 : 0, Hc, Wc,
+                                                              ws);
+  k_tapgrad_final<T><<<C * 9, 256, 0, (hipStream_t)stream>>>(ws, (long long)gr.x * gr.y * gr.z, scale, gw);
+  return launch_status();
+}
+
+template <typename T>
+static int stencil_weight_grad(const T* g, const T* u, const uint8_t* pid, int ntab, T scale, T* gw, double* ws, int B,
+                               int H, int W, void* stream) {
+  if (!g || !u || !gw || !ws || !ntab_ok(ntab) || bad_shape(B, H, W)) return FEA_EINVAL;
+  const dim3 gr = grid_for(H, W, B);
+  k_stencil_wgrad_partial<T><<<gr, kBlock, 0, (hipStream_t)stream>>>(g, u, pid, ntab, H, W, ws);
+  k_tapgrad_final<T><<<ntab * 9, 256, 0, (hipStream_t)stream>>>(ws, (long long)gr.x * gr.y * gr.z, scale, gw);
+  return launch_status();
+}
+
+// The exported symbols: each only forwards to its template.
+#define FEA_GENERIC_API(SUF, T)                                                                                    \
+  extern "C" int fea_knet_apply_##SUF(const T* u, T* y, const uint8_t* pid, const T* ktab, int ntab, int B, int H,  \
+                                      int W, void* stream) {                                                       \
+    return knet_apply<T>(u, y, pid, ktab, ntab, B, H, W, stream);                                                  \
+  }                                                                                                                \
+  extern "C" int fea_split_x_##SUF(const T* x, T* xs, const uint8_t* pid, int C, int B, int H, int W,              \
+                                   void* stream) {                                                                 \
+    return split_x<T>(x, xs, pid, C, B, H, W, stream);                                                             \
+  }                                                                                                                \
+  extern "C" int fea_jacobi_sweep_##SUF(const T* u, const T* f, T* out, const uint8_t* pid, const T* ktab,          \
+                                        const T* omd, int ntab, const T* geo, long long geo_bs, const T* bc,        \
+                                        long long bc_bs, int B, int H, int W, void* stream) {                      \
+    return jacobi_sweep<T>(u, f, out, pid, ktab, omd, ntab, geo, geo_bs, bc, bc_bs, B, H, W, stream);               \
+  }                                                                                                                \
+  extern "C" int fea_jacobi_sweep_pbc_##SUF(const T* u, const T* f, T* out, const T* ktab, const T* omd, int B,    \
+                                            int N, void* stream) {                                                 \
+    return jacobi_sweep_pbc<T>(u, f, out, ktab, omd, B, N, stream);                                                \
+  }                                                                                                                \
+  extern "C" int fea_pbc_pad_##SUF(const T* u, T* dst, int B, int N, int lo, int hi, void* stream) {               \
+    return pbc_pad<T>(u, dst, B, N, lo, hi, stream);                                                               \
+  }                                                                                                                \
+  extern "C" int fea_residual_##SUF(const T* u, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab,      \
+                                    int B, int H, int W, void* stream) {                                           \
+    return residual<T>(u, f, r, pid, ktab, ntab, B, H, W, stream);                                                 \
+  }                                                                                                                \
+  extern "C" int fea_restrict_##SUF(const T* x, int C, T* fc, const uint8_t* pid, const T* rtab, int ntab, T w0,   \
+                                    int B, int H, int W, void* stream) {                                           \
+    return restrict_<T>(x, C, fc, pid, rtab, ntab, w0, B, H, W, stream);                                           \
+  }                                                                                                                \
+  extern "C" int fea_prolong_##SUF(const T* e, int C, T* out, const T* add, const uint8_t* pidc, const T* ptab,     \
+                                   int ntab, T w1, int B, int Hc, int Wc, void* stream) {                          \
+    return prolong<T>(e, C, out, add, pidc, ptab, ntab, w1, B, Hc, Wc, stream);                                    \
+  }                                                                                                                \
+  extern "C" int fea_residual_norm_##SUF(const T* u, const T* f, const uint8_t* pid, const T* ktab, int ntab,       \
+                                         double* out, double* ws, int B, int H, int W, void* stream) {             \
+    return residual_norm<T>(u, f, pid, ktab, ntab, out, ws, B, H, W, stream);                                      \
   }
 
-#define FEA_ADJOINT_API(SUF, T)                                                                          \
-  extern "C" int fea_knet_apply_adj_##SUF(const T* g, T* out, const uint8_t* pid, const T* ktab, int ntab,  \
-                                          int B, int H, int W, void* stream) {                           \
-    if (!g || !out || !ktab || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W) || g == out)     \
-      return FEA_EINVAL;                                                                                 \
-    k_knet_adj<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(g, out, pid, ktab, ntab,  \
-                                                                                  H, W);                 \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_jacobi_sweep_adj_##SUF(const T* g, T* gu, T* gf, const uint8_t* pid, const T* ktab,    \
-                                            const T* omd, int ntab, const T* geo, long long geo_bs, int B,   \
-                                            int H, int W, void* stream) {                                    \
-    if (!g || !gu || !ktab || !omd || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W) || g == gu ||  \
-        g == gf)                                                                                            \
-      return FEA_EINVAL;                                                                                     \
-    k_jacobi_adj<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(g, gu, gf, pid, ktab, omd,  \
-                                                                                    ntab, geo, geo_bs, H, W); \
-    FEA_LAUNCH_CHECK();                                                                                      \
-  }                                                                                                          \
-  extern "C" int fea_restrict_adj_##SUF(const T* g, int C, T* gx, const uint8_t* pid, const T* rtab,     \
-                                        int ntab, T w0, int B, int H, int W, void* stream) {             \
-    if (!g || !gx || !rtab || C < 1 || bad_shape(B, H, W) || H < 3 || W < 3 || !(H & 1) || !(W & 1))      \
-      return FEA_EINVAL;                                                                                 \
-    if ((C == 1 && (ntab < 1 || ntab > FEA_MAX_PATTERNS)) || (C > 1 && (ntab != C || C > FEA_MAX_PATTERNS))) \
-      return FEA_EINVAL;                                                                                 \
-    k_restrict_adj<T><<<grid_for(H, W, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(g, C, gx, pid, rtab, \
-                                                                                      ntab, w0, H, W);   \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_prolong_adj_##SUF(const T* g, int C, T* ge, const uint8_t* pidc, const T* ptab,     \
-                                       int ntab, T w1, int B, int Hc, int Wc, void* stream) {            \
-    if (!g || !ge || !ptab || C < 1 || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2) return FEA_EINVAL;      \
-    if ((C == 1 && (ntab < 1 || ntab > FEA_MAX_PATTERNS)) || (C > 1 && (ntab != C || C > FEA_MAX_PATTERNS))) \
-      return FEA_EINVAL;                                                                                 \
-    k_prolong_adj<T><<<grid_for(Hc, Wc, B), dim3(kBX, kBY), 0, (hipStream_t)stream>>>(g, C, ge, pidc, ptab, \
-                                                                                      ntab, w1, Hc, Wc); \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_transfer_weight_grad_##SUF(const T* cf, int c_split, const T* ff, int f_split, int C,  \
-                                                int interior, T scale, T* gw, double* ws, int B, int Hc,   \
-                                                int Wc, void* stream) {                                  \
-    if (!cf || !ff || !gw || !ws || C < 1 || C > FEA_MAX_PATTERNS || bad_shape(B, Hc, Wc) || Hc < 2 || Wc < 2) \
-      return FEA_EINVAL;                                                                                 \
-    const dim3 gr = grid_for(Hc, Wc, B);                                                                 \
-    k_tapgrad_partial<T><<<gr, dim3(kBX, kBY), 0, (hipStream_t)stream>>>(cf, c_split, ff, f_split, C,    \
-                                                                          interior ? 1 : 0, Hc, Wc, ws);  \
-    k_tapgrad_final<T><<<C * 9, 256, 0, (hipStream_t)stream>>>(ws, (long long)gr.x * gr.y * gr.z, scale, gw); \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" int fea_stencil_weight_grad_##SUF(const T* g, const T* u, const uint8_t* pid, int ntab, T scale, \
-                                               T* gw, double* ws, int B, int H, int W, void* stream) {      \
-    if (!g || !u || !gw || !ws || ntab < 1 || ntab > FEA_MAX_PATTERNS || bad_shape(B, H, W)) return FEA_EINVAL; \
-    const dim3 gr = grid_for(H, W, B);                                                                   \
-    k_stencil_wgrad_partial<T><<<gr, dim3(kBX, kBY), 0, (hipStream_t)stream>>>(g, u, pid, ntab, H, W, ws); \
-    k_tapgrad_final<T><<<ntab * 9, 256, 0, (hipStream_t)stream>>>(ws, (long long)gr.x * gr.y * gr.z, scale, gw); \
-    FEA_LAUNCH_CHECK();                                                                                  \
-  }                                                                                                      \
-  extern "C" size_t fea_stencil_weight_grad_ws_bytes_##SUF(int ntab, int B, int H, int W) {              \
-    const dim3 gr = grid_for(H, W, B);                                                                   \
-    return (size_t)ntab * 9 * gr.x * gr.y * gr.z * sizeof(double);                                       \
-  }                                                                                                      \
-  extern "C" size_t fea_transfer_weight_grad_ws_bytes_##SUF(int C, int B, int Hc, int Wc) {              \
-    const dim3 gr = grid_for(Hc, Wc, B);                                                                 \
-    return (size_t)C * 9 * gr.x * gr.y * gr.z * sizeof(double);                                          \
+#define FEA_ADJOINT_API(SUF, T)                                                                                    \
+  extern "C" int fea_knet_apply_adj_##SUF(const T* g, T* out, const uint8_t* pid, const T* ktab, int ntab, int B,   \
+                                          int H, int W, void* stream) {                                            \
+    return knet_apply_adj<T>(g, out, pid, ktab, ntab, B, H, W, stream);                                            \
+  }                                                                                                                \
+  extern "C" int fea_jacobi_sweep_adj_##SUF(const T* g, T* gu, T* gf, const uint8_t* pid, const T* ktab,            \
+                                            const T* omd, int ntab, const T* geo, long long geo_bs, int B, int H,   \
+                                            int W, void* stream) {                                                 \
+    return jacobi_sweep_adj<T>(g, gu, gf, pid, ktab, omd, ntab, geo, geo_bs, B, H, W, stream);                      \
+  }                                                                                                                \
+  extern "C" int fea_restrict_adj_##SUF(const T* g, int C, T* gx, const uint8_t* pid, const T* rtab, int ntab,      \
+                                        T w0, int B, int H, int W, void* stream) {                                 \
+    return restrict_adj<T>(g, C, gx, pid, rtab, ntab, w0, B, H, W, stream);                                        \
+  }                                                                                                                \
+  extern "C" int fea_prolong_adj_##SUF(const T* g, int C, T* ge, const uint8_t* pidc, const T* ptab, int ntab,      \
+                                       T w1, int B, int Hc, int Wc, void* stream) {                                \
+    return prolong_adj<T>(g, C, ge, pidc, ptab, ntab, w1, B, Hc, Wc, stream);                                      \
+  }                                                                                                                \
+  extern "C" int fea_transfer_weight_grad_##SUF(const T* cf, int c_split, const T* ff, int f_split, int C,          \
+                                                int interior, T scale, T* gw, double* ws, int B, int Hc, int Wc,    \
+                                                void* stream) {                                                    \
+    return transfer_weight_grad<T>(cf, c_split, ff, f_split, C, interior, scale, gw, ws, B, Hc, Wc, stream);        \
+  }                                                                                                                \
+  extern "C" int fea_stencil_weight_grad_##SUF(const T* g, const T* u, const uint8_t* pid, int ntab, T scale,       \
+                                               T* gw, double* ws, int B, int H, int W, void* stream) {             \
+    return stencil_weight_grad<T>(g, u, pid, ntab, scale, gw, ws, B, H, W, stream);                                \
+  }                                                                                                                \
+  extern "C" size_t fea_stencil_weight_grad_ws_bytes_##SUF(int ntab, int B, int H, int W) {                        \
+    return grad_ws_bytes(ntab, B, H, W);                                                                           \
+  }                                                                                                                \
+  extern "C" size_t fea_transfer_weight_grad_ws_bytes_##SUF(int C, int B, int Hc, int Wc) {                        \
+    return grad_ws_bytes(C, B, Hc, Wc);                                                                            \
   }
 
 FEA_GENERIC_API(f32, float)

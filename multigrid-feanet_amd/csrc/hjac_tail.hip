@@ -345,28 +345,34 @@ static inline bool htail_dim_ok(int n, int nlev) {
   return true;
 }
 
-#define FEA_HTAIL_API(SUF, T)                                                                                  \
-  extern "C" int fea_mg_hjac_tail_##SUF(const T* f_t, T* u_t, int Ht, int Wt, int nlev, int ld_t, long long bs_t, \
-                                        const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab,      \
-                                        const T* rtab, const T* ptab, const T* hw, int nlayers, T w0, T w1,     \
-                                        int nu1, int nu2, int B, void* stream) {                               \
-    if (!f_t || !u_t || !ktab || !omd || !rtab || !ptab || (!hw && nlayers > 0) || B <= 0 || B > 65535)        \
-      return FEA_EINVAL;                                                                                       \
-    if (nlev < 1 || nlev > kHTailMaxLevels || nlayers < 0 || nlayers > kHTailMaxLayers || nu1 < 0 || nu2 < 0)   \
-      return FEA_EINVAL;                                                                                       \
-    if (!htail_dim_ok(Ht, nlev) || !htail_dim_ok(Wt, nlev) || ld_t < Wt + 128 / (int)sizeof(T) ||             \
-        bs_t < (long long)(Ht + 2) * ld_t)                                                                     \
-      return FEA_EINVAL;                                                                                       \
-    const bool multi = ntab > 1;                                                                               \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (multi && !pid_levels)) return FEA_EINVAL;                      \
-    if (htail_lds_bytes<T>(Ht, Wt, nlev, multi) > kHTailLdsBytes) return FEA_EINVAL;                          \
-    HTailArgs<T> a{f_t, u_t, pid_levels, ktab, omd, rtab, ptab, hw, w0, w1, Ht, Wt, nlev, ld_t, bs_t, ntab,     \
-                   nlayers, nu1, nu2};                                                                         \
-    hipStream_t s_ = (hipStream_t)stream;                                                                      \
-    if (multi) k_hjac_tail<T, true><<<B, kHTailThreads, 0, s_>>>(a);                                           \
-    else k_hjac_tail<T, false><<<B, kHTailThreads, 0, s_>>>(a);                                                \
-    FEA_LAUNCH_CHECK();                                                                                        \
-  }
+template <typename T>
+static int hjac_tail(const T* f_t, T* u_t, int Ht, int Wt, int nlev, int ld_t, long long bs_t,
+                     const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab, const T* rtab, const T* ptab,
+                     const T* hw, int nlayers, T w0, T w1, int nu1, int nu2, int B, void* stream) {
+  if (!f_t || !u_t || !omd || !rtab || !ptab || (!hw && nlayers > 0) || B <= 0 || B > 65535) return FEA_EINVAL;
+  if (nlev < 1 || nlev > kHTailMaxLevels || nlayers < 0 || nlayers > kHTailMaxLayers || nu1 < 0 || nu2 < 0)
+    return FEA_EINVAL;
+  if (!htail_dim_ok(Ht, nlev) || !htail_dim_ok(Wt, nlev) || ld_t < Wt + 128 / (int)sizeof(T) ||
+      bs_t < (long long)(Ht + 2) * ld_t)
+    return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (!tab_ok(ktab, ntab, pid_levels)) return FEA_EINVAL;
+  if (htail_lds_bytes<T>(Ht, Wt, nlev, multi) > kHTailLdsBytes) return FEA_EINVAL;
+  HTailArgs<T> a{f_t, u_t, pid_levels, ktab, omd, rtab, ptab, hw, w0, w1, Ht, Wt, nlev, ld_t, bs_t, ntab,
+                 nlayers, nu1, nu2};
+  hipStream_t s_ = (hipStream_t)stream;
+  if (multi) k_hjac_tail<T, true><<<B, kHTailThreads, 0, s_>>>(a);
+  else k_hjac_tail<T, false><<<B, kHTailThreads, 0, s_>>>(a);
+  return launch_status();
+}
 
+#define FEA_HTAIL_API(SUF, T)                                                                                     \
+  extern "C" int fea_mg_hjac_tail_##SUF(const T* f_t, T* u_t, int Ht, int Wt, int nlev, int ld_t, long long bs_t,  \
+                                        const uint8_t* pid_levels, const T* ktab, const T* omd, int ntab,         \
+                                        const T* rtab, const T* ptab, const T* hw, int nlayers, T w0, T w1,        \
+                                        int nu1, int nu2, int B, void* stream) {                                  \
+    return hjac_tail<T>(f_t, u_t, Ht, Wt, nlev, ld_t, bs_t, pid_levels, ktab, omd, ntab, rtab, ptab, hw, nlayers,  \
+                        w0, w1, nu1, nu2, B, stream);                                                             \
+  }
 FEA_HTAIL_API(f32, float)
 FEA_HTAIL_API(f64, double)

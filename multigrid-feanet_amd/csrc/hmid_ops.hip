@@ -532,66 +532,77 @@ static int hm_fill(HMArgs<T>& a, int B, int H, int W, int nl, int TT) {
   return 0;
 }
 
-#define FEA_HMID_API(SUF, T)                                                                                       \
-  extern "C" int fea_mg_hmid_down_##SUF(const T* const* f, T* const* u, const uint8_t* const* pid, int B, int H,   \
-                                        int W, const T* ktab, const T* omd, int ntab, const T* hw, int nlayers,    \
-                                        const T* rtab, int nrtab, T w0, int TT, void* stream) {                    \
-    HMArgs<T> a = {};                                                                                              \
-    if (!f || !u || !ktab || !omd || !rtab || (!hw && nlayers > 0) || ntab < 1 || ntab > FEA_MAX_PATTERNS)        \
-      return FEA_EINVAL;                                                                                           \
-    const bool multi = ntab > 1;                                                                                   \
-    if ((multi && (!pid || nrtab != ntab)) || (!multi && nrtab != 1)) return FEA_EINVAL;                          \
-    if (hm_fill<T>(a, B, H, W, nlayers, TT)) return FEA_EINVAL;                                                    \
-    if (hm_down_lds(TT, nlayers, (int)sizeof(T), multi) > kHMLdsBytes) return FEA_EINVAL;                          \
-    for (int j = 0; j < 3; ++j) {                                                                                  \
-      if (!f[j] || (j < 2 && (!u[j] || u[j] == f[j])) || (multi && j < 2 && !pid[j])) return FEA_EINVAL;         \
-      a.f[j] = f[j];                                                                                               \
-      a.fo[j] = const_cast<T*>(f[j]);                                                                              \
-      a.pid[j] = multi && j < 2 ? pid[j] : nullptr;                                                                \
-    }                                                                                                              \
-    a.uo[0] = u[0];                                                                                                \
-    a.uo[1] = u[1];                                                                                                \
-    a.ktab = ktab; a.omd = omd; a.xtab = rtab; a.hw = hw; a.w = w0; a.ntab = ntab; a.nx = nrtab;                  \
-    a.ntr = (a.H[2] - 2 + TT - 1) / TT;                                                                            \
-    a.ntc = (a.W[2] - 2 + TT - 1) / TT;                                                                            \
-    const dim3 grid(B * a.ntr * a.ntc);                                                                            \
-    hipStream_t s_ = (hipStream_t)stream;                                                                          \
-    if (multi) k_hmid_down<T, true><<<grid, kHMThreads, 0, s_>>>(a);                                               \
-    else k_hmid_down<T, false><<<grid, kHMThreads, 0, s_>>>(a);                                                    \
-    FEA_LAUNCH_CHECK();                                                                                            \
-  }                                                                                                                \
-  extern "C" int fea_mg_hmid_up_##SUF(const T* const* f, const T* const* u, const T* e, T* out,                    \
-                                      const uint8_t* const* pid, int B, int H, int W, const T* ktab, const T* omd, \
-                                      int ntab, const T* hw, int nlayers, const T* ptab, int nptab, T w1, int TT,  \
-                                      void* stream) {                                                              \
-    HMArgs<T> a = {};                                                                                              \
-    if (!f || !u || !e || !out || !ktab || !omd || !ptab || (!hw && nlayers > 0) || ntab < 1 ||                    \
-        ntab > FEA_MAX_PATTERNS)                                                                                   \
-      return FEA_EINVAL;                                                                                           \
-    const bool multi = ntab > 1;                                                                                   \
-    if ((multi && (!pid || nptab != ntab)) || (!multi && nptab != 1)) return FEA_EINVAL;                          \
-    if (hm_fill<T>(a, B, H, W, nlayers, TT)) return FEA_EINVAL;                                                    \
-    if (hm_up_lds(TT, nlayers, (int)sizeof(T), multi) > kHMLdsBytes) return FEA_EINVAL;                            \
-    for (int j = 0; j < 3; ++j)                                                                                    \
-      if (multi && !pid[j]) return FEA_EINVAL;                                                                     \
-    for (int j = 0; j < 2; ++j) {                                                                                  \
-      if (!f[j] || !u[j] || (j == 0 && (out == f[j] || out == u[j]))) return FEA_EINVAL;                           \
-      a.f[j] = f[j];                                                                                               \
-      a.u[j] = u[j];                                                                                               \
-    }                                                                                                              \
-    if (out == e) return FEA_EINVAL;                                                                               \
-    for (int j = 0; j < 3; ++j) a.pid[j] = multi ? pid[j] : nullptr;                                               \
-    a.e = e; a.out = out;                                                                                          \
-    a.ktab = ktab; a.omd = omd; a.xtab = ptab; a.hw = hw; a.w = w1; a.ntab = ntab; a.nx = nptab;                  \
-    a.ntr = (a.H[0] - 2 + TT - 1) / TT;                                                                            \
-    a.ntc = (a.W[0] - 2 + TT - 1) / TT;                                                                            \
-    const dim3 grid(B * a.ntr * a.ntc);                                                                            \
-    hipStream_t s_ = (hipStream_t)stream;                                                                          \
-    if (multi) k_hmid_up<T, true><<<grid, kHMThreads, 0, s_>>>(a);                                                 \
-    else k_hmid_up<T, false><<<grid, kHMThreads, 0, s_>>>(a);                                                      \
-    FEA_LAUNCH_CHECK();                                                                                            \
+template <typename T>
+static int hmid_down(const T* const* f, T* const* u, const uint8_t* const* pid, int B, int H, int W, const T* ktab,
+                     const T* omd, int ntab, const T* hw, int nlayers, const T* rtab, int nrtab, T w0, int TT,
+                     void* stream) {
+  HMArgs<T> a = {};
+  if (!f || !u || !omd || !rtab || (!hw && nlayers > 0) || !tab_ok(ktab, ntab, pid) || !xtab_ok(nrtab, ntab))
+    return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (hm_fill<T>(a, B, H, W, nlayers, TT)) return FEA_EINVAL;
+  if (hm_down_lds(TT, nlayers, (int)sizeof(T), multi) > kHMLdsBytes) return FEA_EINVAL;
+  for (int j = 0; j < 3; ++j) {
+    if (!f[j] || (j < 2 && (!u[j] || u[j] == f[j])) || (multi && j < 2 && !pid[j])) return FEA_EINVAL;
+    a.f[j] = f[j];
+    a.fo[j] = const_cast<T*>(f[j]);
+    a.pid[j] = multi && j < 2 ? pid[j] : nullptr;
   }
+  a.uo[0] = u[0];
+  a.uo[1] = u[1];
+  a.ktab = ktab; a.omd = omd; a.xtab = rtab; a.hw = hw; a.w = w0; a.ntab = ntab; a.nx = nrtab;
+  a.ntr = (a.H[2] - 2 + TT - 1) / TT;
+  a.ntc = (a.W[2] - 2 + TT - 1) / TT;
+  const dim3 grid(B * a.ntr * a.ntc);
+  hipStream_t s_ = (hipStream_t)stream;
+  if (multi) k_hmid_down<T, true><<<grid, kHMThreads, 0, s_>>>(a);
+  else k_hmid_down<T, false><<<grid, kHMThreads, 0, s_>>>(a);
+  return launch_status();
+}
 
+template <typename T>
+static int hmid_up(const T* const* f, const T* const* u, const T* e, T* out, const uint8_t* const* pid, int B, int H,
+                   int W, const T* ktab, const T* omd, int ntab, const T* hw, int nlayers, const T* ptab, int nptab,
+                   T w1, int TT, void* stream) {
+  HMArgs<T> a = {};
+  if (!f || !u || !e || !out || !omd || !ptab || (!hw && nlayers > 0) || !tab_ok(ktab, ntab, pid) ||
+      !xtab_ok(nptab, ntab))
+    return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (hm_fill<T>(a, B, H, W, nlayers, TT)) return FEA_EINVAL;
+  if (hm_up_lds(TT, nlayers, (int)sizeof(T), multi) > kHMLdsBytes) return FEA_EINVAL;
+  for (int j = 0; j < 3; ++j)
+    if (multi && !pid[j]) return FEA_EINVAL;
+  for (int j = 0; j < 2; ++j) {
+    if (!f[j] || !u[j] || (j == 0 && (out == f[j] || out == u[j]))) return FEA_EINVAL;
+    a.f[j] = f[j];
+    a.u[j] = u[j];
+  }
+  if (out == e) return FEA_EINVAL;
+  for (int j = 0; j < 3; ++j) a.pid[j] = multi ? pid[j] : nullptr;
+  a.e = e; a.out = out;
+  a.ktab = ktab; a.omd = omd; a.xtab = ptab; a.hw = hw; a.w = w1; a.ntab = ntab; a.nx = nptab;
+  a.ntr = (a.H[0] - 2 + TT - 1) / TT;
+  a.ntc = (a.W[0] - 2 + TT - 1) / TT;
+  const dim3 grid(B * a.ntr * a.ntc);
+  hipStream_t s_ = (hipStream_t)stream;
+  if (multi) k_hmid_up<T, true><<<grid, kHMThreads, 0, s_>>>(a);
+  else k_hmid_up<T, false><<<grid, kHMThreads, 0, s_>>>(a);
+  return launch_status();
+}
+
+#define FEA_HMID_API(SUF, T)                                                                                        \
+  extern "C" int fea_mg_hmid_down_##SUF(const T* const* f, T* const* u, const uint8_t* const* pid, int B, int H,     \
+                                        int W, const T* ktab, const T* omd, int ntab, const T* hw, int nlayers,      \
+                                        const T* rtab, int nrtab, T w0, int TT, void* stream) {                     \
+    return hmid_down<T>(f, u, pid, B, H, W, ktab, omd, ntab, hw, nlayers, rtab, nrtab, w0, TT, stream);             \
+  }                                                                                                                 \
+  extern "C" int fea_mg_hmid_up_##SUF(const T* const* f, const T* const* u, const T* e, T* out,                     \
+                                      const uint8_t* const* pid, int B, int H, int W, const T* ktab, const T* omd,  \
+                                      int ntab, const T* hw, int nlayers, const T* ptab, int nptab, T w1, int TT,   \
+                                      void* stream) {                                                               \
+    return hmid_up<T>(f, u, e, out, pid, B, H, W, ktab, omd, ntab, hw, nlayers, ptab, nptab, w1, TT, stream);       \
+  }
 FEA_HMID_API(f32, float)
 FEA_HMID_API(f64, double)
 

@@ -219,21 +219,13 @@ __device__ __forceinline__ void hs_rows(int t, int rb, int H, int Hc, int& r0, i
   }
 }
 
-// FEA_HS_INNER (lab): a wave whose task lies inside the grid with its whole reach (every row it streams, every column
-// its lanes load, every coarse row it reads) runs the EDGE = false body: no boundary / edge selects (j - u, the masked
-// HNet stages, the prolonged correction, the out row's stand-in values), no row or lane clamps, no partial stores,
-// no loads of the iterate's boundary values.  Same per-node expressions: bitwise the general body (GPU hnet tests
-// pass with it).  Measured slower, so off: the interior body has 19 % fewer VALU per step (800 vs 990 per 6-step
-// loop of the fp64 sweep + restriction, same 231 VGPRs) yet the 4097^2 MG-HJac cycle ran 411 instead of 396 us
-// (fea_mg_hsweep_restrict 123 vs 111 us, same lease, three alternations; profiles/r06_ab/hjac_inner_rejected.txt):
-// the kernel then carries both bodies (7186 instead of 4290 instructions) and waves of both kinds share each CU's
-// instruction cache.
-#ifndef FEA_HS_INNER
-#define FEA_HS_INNER 0
-#endif
+// One body serves every task, with boundary selects, clamps and partial stores throughout: a second, select-free body
+// for tasks wholly inside the grid measured slower although it has 19 % fewer VALU per step (4097^2 MG-HJac cycle 411
+// instead of 396 us: the kernel then carries both bodies and waves of both kinds share each CU's instruction cache;
+// profiles/r06_ab/hjac_inner_rejected.txt).
 
 // One (row task, strip) of the streaming sweep (see k_mg_hsweep_strip).
-template <typename T, bool MULTI, bool ZERO, bool RAW, int NL, int MODE, bool EDGE>
+template <typename T, bool MULTI, bool ZERO, bool RAW, int NL, int MODE>
 __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, int s, const T* tab, const T* tb2) {
   static_assert(MODE != 1 || !ZERO, "the prolongation variant corrects a stored iterate");
   using G = HSGeo<T, NL, MODE>;
@@ -247,15 +239,15 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
   const int H = g.H, W = g.W, ld = g.ld;
   const int cs = 1 + s * S - HLN * V;  // first loaded column
   const int cl = cs + V * lane;
-  const int ll = EDGE ? min(lane, (W - 1 - cs) / V) : lane;  // lanes past the last column re-read a valid line
+  const int ll = min(lane, (W - 1 - cs) / V);  // lanes past the last column re-read a valid line
   const bool own = lane >= HLN && lane < 64 - HLN;
   int r0, r1, rc0, rc1, I0, I1;
   hs_rows<MODE>(t, g.rb, H, g.Hc, r0, r1, rc0, rc1, I0, I1);
   bool cin[V], cgr[V];
 #pragma unroll
   for (int k = 0; k < V; ++k) {
-    cin[k] = !EDGE || (cl + k >= 1 && cl + k <= W - 2);
-    cgr[k] = !EDGE || (cl + k >= 0 && cl + k <= W - 1);
+    cin[k] = cl + k >= 1 && cl + k <= W - 2;
+    cgr[k] = cl + k >= 0 && cl + k <= W - 1;
   }
   T ks[9], om = 0, hk[NL > 0 ? NL : 1][9], t2[9];
   if constexpr (!MULTI) {
@@ -277,13 +269,13 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
   T* __restrict__ ob = g.out + boff;
   const uint8_t* __restrict__ pb = MULTI ? g.pid + OFF + cs : nullptr;
   auto rowo = [&](int r) -> long long {
-    if constexpr (EDGE) r = min(max(r, -1), H);
+    r = min(max(r, -1), H);
     return (long long)(r + 1) * ld + V * ll;
   };
 
   // MODE 1: the lane's coarse values (cl + 1) / 2 + q, q < Q, and the left lane's last one (DPP)
   const int jc = (cs + 1) / 2;
-  const int llc = MODE == 1 ? (EDGE ? min(lane, (g.Wc - 1 - jc) / Q) : lane) : 0;
+  const int llc = MODE == 1 ? min(lane, (g.Wc - 1 - jc) / Q) : 0;
   const T* __restrict__ eb = MODE == 1 ? g.ec + (long long)b * g.bsc + OFF + jc + Q * llc : nullptr;
   const uint8_t* __restrict__ pcb = (MODE == 1 && MULTI) ? g.pidc + OFF + jc + Q * llc : nullptr;
   struct CR {  // coarse row: e[0] = column (cl-1)/2 (left lane), e[1..Q] = own; pattern offsets o[]
@@ -296,7 +288,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
   };
   auto crow_ld = [&](int a) {
     CRaw r;
-    if constexpr (EDGE) a = min(max(a, -1), g.Hc);
+    a = min(max(a, -1), g.Hc);
     const long long o = (long long)(a + 1) * g.ldc;
     if constexpr (MODE == 1) {
       if constexpr (Q == 1) {
@@ -363,7 +355,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
   T ur[PF][V], fr_[PF][V], rw_[PF][V], frr[PF][V], uo[PF][V];
   int pr[PF][V], po[PF][V];
   // MODE 2 needs the iterate's values of an out row only where they stand in for the sweep (boundary nodes)
-  auto need_uo = [&](int yy) { return EDGE && (!(yy >= 1 && yy <= H - 2) || !cin[0] || !cin[V - 1]); };
+  auto need_uo = [&](int yy) { return !(yy >= 1 && yy <= H - 2) || !cin[0] || !cin[V - 1]; };
   auto fill = [&](int sl, int y) {
 #pragma unroll
     for (int k = 0; k < V; ++k) ur[sl][k] = T(0);
@@ -374,7 +366,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
     if constexpr (MODE == 2) {
       hload<T, V>(fb + rowo(y - 2 - NL), frr[sl]);
       if constexpr (MULTI) hpload<V>(pb + rowo(y - 1 - NL), po[sl]);
-      if constexpr (!ZERO && EDGE) {
+      if constexpr (!ZERO) {
 #pragma unroll
         for (int k = 0; k < V; ++k) uo[sl][k] = T(0);
         if (need_uo(y - 1 - NL)) hload<T, V>(ub + rowo(y - 1 - NL), uo[sl]);
@@ -430,14 +422,14 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
       py[k] = MULTI ? pr[SL][k] : 0;
       raw[k] = RAW ? rw_[SL][k] : T(0);
       fres[k] = MODE == 2 ? frr[SL][k] : T(0);
-      uout[k] = (MODE == 2 && !ZERO && EDGE) ? uo[SL][k] : T(0);
+      uout[k] = (MODE == 2 && !ZERO) ? uo[SL][k] : T(0);
       pout[k] = (MODE == 2 && MULTI) ? po[SL][k] : 0;
     }
     fill(SL, y + PF);  // (rows past the task's last are clamped into the frame: loaded, never used)
     if constexpr (MODE == 1) {
       stage_t2();
       // x(y) = u(y) + w1 P(ec) on the interior (correct_even / correct_odd of k_mg_prolong)
-      const bool yin = !EDGE || (y >= 1 && y <= H - 2);
+      const bool yin = y >= 1 && y <= H - 2;
 #pragma unroll
       for (int k = 0; k < V; ++k) {  // (branch-free: a select, not a divergent branch per column)
         T xk;
@@ -466,7 +458,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
     // j and d_0 of row y-1
     stage_ks();
     const int yj = y - 1;
-    const bool rin = !EDGE || (yj >= 1 && yj <= H - 2), rgr = !EDGE || (yj >= 0 && yj <= H - 1);
+    const bool rin = yj >= 1 && yj <= H - 2, rgr = yj >= 0 && yj <= H - 1;
     T d0[V], jv[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
@@ -526,7 +518,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
     for (int l = 1; l <= NL; ++l) {
       stage_hk(l - 1);
       const int yl = y - 1 - l;
-      const bool lin = !EDGE || (yl >= 1 && yl <= H - 2);
+      const bool lin = yl >= 1 && yl <= H - 2;
       T dl[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -556,7 +548,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
     if (own && yo >= r0 && yo < r1) hstore<T, V>(ob + (long long)(yo + 1) * ld + V * lane, o, cin);
     if constexpr (MODE == 2) {
       // the out row as the buffer would hold it: the iterate's own values off the interior
-      const bool oin = !EDGE || (yo >= 1 && yo <= H - 2);
+      const bool oin = yo >= 1 && yo <= H - 2;
 #pragma unroll
       for (int k = 0; k < V; ++k) o[k] = (oin && cin[k]) ? o[k] : uout[k];
       O0 = O1;
@@ -640,7 +632,7 @@ __device__ __forceinline__ void hsweep_task(const HSArgs<T>& g, int b, int t, in
               T* cp = g.fc + (long long)b * g.bsc + OFF + (long long)(I + 1) * g.ldc + Jl;
 #pragma unroll
               for (int q = 0; q < Q; ++q)
-                if (!EDGE || Jl + q <= g.Wc - 2) cp[q] = oc[q];
+                if (Jl + q <= g.Wc - 2) cp[q] = oc[q];
             }
           }
 #pragma unroll
@@ -683,21 +675,7 @@ __attribute__((amdgpu_waves_per_eu(hs_mode1_wide<T, MULTI, MODE, RAW>() ? 3 : 1)
   const int w = (bid - b * wpb) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (w >= per) return;
   const int t = w / g.nstrips, s = w - t * g.nstrips;
-  if constexpr (FEA_HS_INNER != 0) {
-    // interior: the rows streamed (from the first fill step 2 + NL rows above the first computed one, through the
-    // prefetch past the last), the loaded columns and (MODE 1) the coarse rows read all lie strictly inside the grid
-    int r0, r1, rc0, rc1, I0, I1;
-    hs_rows<MODE>(t, g.rb, g.H, g.Hc, r0, r1, rc0, rc1, I0, I1);
-    const int cs = 1 + s * G::S - G::HLN * V;
-    const int ya = ((rc0 - G::HALO) & ~1) - 3 - NL, yz = rc1 + G::HALO + 4;
-    const bool inner = cs >= 1 && cs + 64 * V - 1 <= g.W - 2 && ya >= 1 && yz <= g.H - 2 &&
-                       (MODE != 1 || ((ya >> 1) - 1 >= 1 && (yz >> 1) + 4 <= g.Hc - 2));
-    if (__builtin_amdgcn_readfirstlane((int)inner)) {  // wave-uniform (scalar branch)
-      hsweep_task<T, MULTI, ZERO, RAW, NL, MODE, false>(g, b, t, s, tab, tb2);
-      return;
-    }
-  }
-  hsweep_task<T, MULTI, ZERO, RAW, NL, MODE, true>(g, b, t, s, tab, tb2);
+  hsweep_task<T, MULTI, ZERO, RAW, NL, MODE>(g, b, t, s, tab, tb2);
 }
 
 }  // namespace fea
@@ -748,10 +726,6 @@ static int hs_num_cus() {
   return cached[dev];
 }
 
-#ifndef FEA_HSWEEP_BALANCED
-#define FEA_HSWEEP_BALANCED 1
-#endif
-
 // Row tasks: `unit` rows each (MODE 2 counts coarse rows, 2 fine rows per unit), a task streams k*unit + ovh
 // rows (the stage chain's halo rows above and below its own).  Balanced (the cycle join's rule, framed_ops.hip
 // balanced_rb): the slowest CU runs ceil(workgroups / CUs) tasks back to back, so the cost of a task height is
@@ -766,7 +740,6 @@ static int hs_num_cus() {
 #define FEA_HS_MINW 1536
 #endif
 static int hs_units_per_task(int B, int nstrips, int rows_u, int k, int ovh) {
-#if FEA_HSWEEP_BALANCED
   const long long ncu = hs_num_cus();
   long long best_ok = -1, best_any = -1;
   int u_ok = 0, u_any = 1;
@@ -778,12 +751,6 @@ static int hs_units_per_task(int B, int nstrips, int rows_u, int k, int ovh) {
     if (best_any < 0 || cost < best_any) best_any = cost, u_any = u;
   }
   return best_ok >= 0 ? u_ok : u_any;
-#else
-  // the largest of 64 / 32 / 16 / 8 rows that still gives >= 2048 waves
-  for (int rb = 64; rb > 8; rb /= 2)
-    if ((long long)B * nstrips * ((rows_u * k + rb - 1) / rb) >= 2048) return rb / k;
-  return 8 / k;
-#endif
 }
 
 template <typename T, int MODE>
@@ -801,71 +768,87 @@ static int hsweep_launch(HSArgs<T> g, int nl, int B, hipStream_t s) {
   g.ntr = (rows + u - 1) / u;
   const dim3 grid((unsigned)(B * ((g.ntr * g.nstrips + 3) / 4)));
   hs_dispatch<T, MODE>(g.ntab > 1, !g.u, g.u_raw != nullptr, nl, grid, s, g);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
 static inline bool hs_layout_ok(int H, int W, int ld, long long bs, int esz) {
   return H >= 3 && W >= 3 && ld >= W + 128 / esz && bs >= (long long)(H + 2) * ld;
 }
 
-#define FEA_HNET_API(SUF, T)                                                                                \
-  extern "C" int fea_mg_hsweep_##SUF(const T* u, const T* u_raw, const T* f, T* out, const uint8_t* pid,     \
-                                     const T* ktab,                                                          \
-                                     const T* omd, int ntab, const T* hw, int nlayers, int B, int H, int W,  \
-                                     int ld, long long bs, void* stream) {                                   \
-    if (!f || !out || !ktab || !omd || (!hw && nlayers > 0) || out == u || B <= 0 || B > 65535) return FEA_EINVAL; \
-    if (nlayers < 0 || nlayers > kHMaxLayers || !hs_layout_ok(H, W, ld, bs, sizeof(T))) return FEA_EINVAL;    \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid)) return FEA_EINVAL;                         \
-    if (u_raw && !u) return FEA_EINVAL;                                                                      \
-    HSArgs<T> g{};                                                                                           \
-    g.u = u; g.u_raw = u_raw; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.hw = hw;       \
-    g.ntab = ntab; g.H = H; g.W = W; g.ld = ld; g.bs = bs;                                                    \
-    return hsweep_launch<T, 0>(g, nlayers, B, (hipStream_t)stream);                                          \
-  }                                                                                                          \
-  extern "C" int fea_mg_hsweep_restrict_##SUF(const T* u, const T* u_raw, const T* f, T* out, T* fc,           \
-                                              const uint8_t* pid, const T* ktab, const T* omd, int ntab,       \
-                                              const T* hw, int nlayers, const T* rtab, int nrtab, T w0, int B,  \
-                                              int H, int W, int ld, long long bs, int ldc, long long bsc,       \
-                                              void* stream) {                                                  \
-    if (!f || !out || !fc || !ktab || !omd || !rtab || (!hw && nlayers > 0) || out == u || B <= 0 ||         \
-        B > 65535)                                                                                           \
-      return FEA_EINVAL;                                                                                     \
-    if (nlayers < 0 || nlayers > kHMaxLayers || !hs_layout_ok(H, W, ld, bs, sizeof(T)) || !(H & 1) || !(W & 1)) \
-      return FEA_EINVAL;                                                                                     \
-    const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;                                                            \
-    if (!hs_layout_ok(Hc, Wc, ldc, bsc, sizeof(T))) return FEA_EINVAL;                                        \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (ntab > 1 && !pid) || (nrtab != ntab && nrtab != 1) ||        \
-        (ntab > 1 && nrtab == 1))                                                                            \
-      return FEA_EINVAL;                                                                                     \
-    if (u_raw && !u) return FEA_EINVAL;                                                                      \
-    HSArgs<T> g{};                                                                                           \
-    g.u = u; g.u_raw = u_raw; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.hw = hw;       \
-    g.ntab = ntab; g.H = H; g.W = W; g.ld = ld; g.bs = bs;                                                    \
-    g.fc = fc; g.rtab = rtab; g.w0 = w0; g.Hc = Hc; g.Wc = Wc; g.ldc = ldc; g.bsc = bsc;                      \
-    return hsweep_launch<T, 2>(g, nlayers, B, (hipStream_t)stream);                                          \
-  }                                                                                                          \
-  extern "C" int fea_mg_prolong_hsweep_##SUF(const T* u, const T* u_raw, const T* ec, const T* f, T* out,       \
-                                             const uint8_t* pid,                                               \
-                                             const uint8_t* pidc, const T* ktab, const T* omd, int ntab,        \
-                                             const T* hw, int nlayers, const T* ptab, int nptab, T w1, int B,   \
-                                             int H, int W, int ld, long long bs, int ldc, long long bsc,        \
-                                             void* stream) {                                                   \
-    if (!u || !ec || !f || !out || !ktab || !omd || !ptab || (!hw && nlayers > 0) || out == u || B <= 0 ||   \
-        B > 65535)                                                                                           \
-      return FEA_EINVAL;                                                                                     \
-    if (nlayers < 0 || nlayers > kHMaxLayers || !hs_layout_ok(H, W, ld, bs, sizeof(T)) || !(H & 1) || !(W & 1)) \
-      return FEA_EINVAL;                                                                                     \
-    const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;                                                            \
-    if (!hs_layout_ok(Hc, Wc, ldc, bsc, sizeof(T))) return FEA_EINVAL;                                        \
-    if (ntab < 1 || ntab > FEA_MAX_PATTERNS || (nptab != ntab && nptab != 1) ||                              \
-        (ntab > 1 && (!pid || !pidc || nptab == 1)))                                                          \
-      return FEA_EINVAL;                                                                                     \
-    HSArgs<T> g{};                                                                                           \
-    g.u = u; g.u_raw = u_raw; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.hw = hw;       \
-    g.ntab = ntab; g.H = H; g.W = W; g.ld = ld; g.bs = bs;                                                    \
-    g.ec = ec; g.pidc = pidc; g.ptab = ptab; g.w1 = w1; g.Hc = Hc; g.Wc = Wc; g.ldc = ldc; g.bsc = bsc;       \
-    return hsweep_launch<T, 1>(g, nlayers, B, (hipStream_t)stream);                                          \
-  }
+// What the three entry points share: the sweep's operands, its layout and layer count (false: invalid arguments).
+template <typename T>
+static bool hs_args(HSArgs<T>& g, const T* u, const T* u_raw, const T* f, T* out, const uint8_t* pid, const T* ktab,
+                    const T* omd, int ntab, const T* hw, int nlayers, int B, int H, int W, int ld, long long bs) {
+  if (!f || !out || !omd || (!hw && nlayers > 0) || out == u || (u_raw && !u) || B <= 0 || B > 65535) return false;
+  if (nlayers < 0 || nlayers > kHMaxLayers || !hs_layout_ok(H, W, ld, bs, sizeof(T)) || !tab_ok(ktab, ntab, pid))
+    return false;
+  g = HSArgs<T>{};
+  g.u = u; g.u_raw = u_raw; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.hw = hw;
+  g.ntab = ntab; g.H = H; g.W = W; g.ld = ld; g.bs = bs;
+  return true;
+}
 
+// the coarse grid of the two intergrid entry points: odd fine sizes, its own layout
+template <typename T>
+static bool hs_coarse(HSArgs<T>& g, int ldc, long long bsc) {
+  g.Hc = (g.H + 1) / 2; g.Wc = (g.W + 1) / 2; g.ldc = ldc; g.bsc = bsc;
+  return (g.H & 1) && (g.W & 1) && hs_layout_ok(g.Hc, g.Wc, ldc, bsc, sizeof(T));
+}
+
+template <typename T>
+static int hsweep(const T* u, const T* u_raw, const T* f, T* out, const uint8_t* pid, const T* ktab, const T* omd,
+                  int ntab, const T* hw, int nlayers, int B, int H, int W, int ld, long long bs, void* stream) {
+  HSArgs<T> g;
+  if (!hs_args(g, u, u_raw, f, out, pid, ktab, omd, ntab, hw, nlayers, B, H, W, ld, bs)) return FEA_EINVAL;
+  return hsweep_launch<T, 0>(g, nlayers, B, (hipStream_t)stream);
+}
+
+template <typename T>
+static int hsweep_restrict(const T* u, const T* u_raw, const T* f, T* out, T* fc, const uint8_t* pid, const T* ktab,
+                           const T* omd, int ntab, const T* hw, int nlayers, const T* rtab, int nrtab, T w0, int B,
+                           int H, int W, int ld, long long bs, int ldc, long long bsc, void* stream) {
+  HSArgs<T> g;
+  if (!fc || !rtab || !hs_args(g, u, u_raw, f, out, pid, ktab, omd, ntab, hw, nlayers, B, H, W, ld, bs) ||
+      !hs_coarse(g, ldc, bsc) || !xtab_ok(nrtab, ntab))
+    return FEA_EINVAL;
+  g.fc = fc; g.rtab = rtab; g.w0 = w0;
+  return hsweep_launch<T, 2>(g, nlayers, B, (hipStream_t)stream);
+}
+
+template <typename T>
+static int prolong_hsweep(const T* u, const T* u_raw, const T* ec, const T* f, T* out, const uint8_t* pid,
+                          const uint8_t* pidc, const T* ktab, const T* omd, int ntab, const T* hw, int nlayers,
+                          const T* ptab, int nptab, T w1, int B, int H, int W, int ld, long long bs, int ldc,
+                          long long bsc, void* stream) {
+  HSArgs<T> g;
+  if (!u || !ec || !ptab || !hs_args(g, u, u_raw, f, out, pid, ktab, omd, ntab, hw, nlayers, B, H, W, ld, bs) ||
+      !hs_coarse(g, ldc, bsc) || (ntab > 1 && !pidc) || !xtab_ok(nptab, ntab))
+    return FEA_EINVAL;
+  g.ec = ec; g.pidc = pidc; g.ptab = ptab; g.w1 = w1;
+  return hsweep_launch<T, 1>(g, nlayers, B, (hipStream_t)stream);
+}
+
+#define FEA_HNET_API(SUF, T)                                                                                       \
+  extern "C" int fea_mg_hsweep_##SUF(const T* u, const T* u_raw, const T* f, T* out, const uint8_t* pid,            \
+                                     const T* ktab, const T* omd, int ntab, const T* hw, int nlayers, int B, int H, \
+                                     int W, int ld, long long bs, void* stream) {                                  \
+    return hsweep<T>(u, u_raw, f, out, pid, ktab, omd, ntab, hw, nlayers, B, H, W, ld, bs, stream);                \
+  }                                                                                                                \
+  extern "C" int fea_mg_hsweep_restrict_##SUF(const T* u, const T* u_raw, const T* f, T* out, T* fc,                \
+                                              const uint8_t* pid, const T* ktab, const T* omd, int ntab,            \
+                                              const T* hw, int nlayers, const T* rtab, int nrtab, T w0, int B,      \
+                                              int H, int W, int ld, long long bs, int ldc, long long bsc,           \
+                                              void* stream) {                                                      \
+    return hsweep_restrict<T>(u, u_raw, f, out, fc, pid, ktab, omd, ntab, hw, nlayers, rtab, nrtab, w0, B, H, W, ld, \
+                              bs, ldc, bsc, stream);                                                               \
+  }                                                                                                                \
+  extern "C" int fea_mg_prolong_hsweep_##SUF(const T* u, const T* u_raw, const T* ec, const T* f, T* out,           \
+                                             const uint8_t* pid, const uint8_t* pidc, const T* ktab, const T* omd,  \
+                                             int ntab, const T* hw, int nlayers, const T* ptab, int nptab, T w1,    \
+                                             int B, int H, int W, int ld, long long bs, int ldc, long long bsc,     \
+                                             void* stream) {                                                       \
+    return prolong_hsweep<T>(u, u_raw, ec, f, out, pid, pidc, ktab, omd, ntab, hw, nlayers, ptab, nptab, w1, B, H,  \
+                             W, ld, bs, ldc, bsc, stream);                                                         \
+  }
 FEA_HNET_API(f32, float)
 FEA_HNET_API(f64, double)

@@ -748,89 +748,87 @@ static void mid_launch(Kern k1, Kern k2, Kern k3, Kern k4, int k, dim3 grid, voi
   hipLaunchKernelGGL(kern, grid, dim3(kMidThreads), 0, (hipStream_t)stream, a);
 }
 
-#define FEA_MID_API(SUF, T)                                                                                      \
-  extern "C" int fea_mg_mid_down_##SUF(const T* const* f, const uint8_t* const* pid, int k, int B, int H, int W, \
-                                       const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab, T w0,    \
-                                       int TR, int TC, void* stream) {                                          \
-    MidArgs<T> a = {};                                                                                           \
-    if (!f || !ktab || !omd || !rtab || ntab < 1 || ntab > FEA_MAX_PATTERNS) return FEA_EINVAL;                \
-    const bool multi = ntab > 1;                                                                                 \
-    if ((multi && (!pid || nrtab != ntab)) || (!multi && nrtab != 1)) return FEA_EINVAL;                        \
-    if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;                                                   \
-    if (mid_down_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;                       \
-    for (int j = 0; j <= k; ++j) {                                                                               \
-      if (!f[j] || (multi && j < k && !pid[j])) return FEA_EINVAL;                                              \
-      a.f[j] = f[j];                                                                                             \
-      a.fo[j] = const_cast<T*>(f[j]);                                                                            \
-      a.pid[j] = multi && j < k ? pid[j] : nullptr;                                                              \
-    }                                                                                                            \
-    a.ktab = ktab; a.omd = omd; a.xtab = rtab; a.w = w0; a.ntab = ntab; a.nx = nrtab;                           \
-    a.ntr = (a.H[k] - 2 + TR - 1) / TR;                                                                          \
-    a.ntc = (a.W[k] - 2 + TC - 1) / TC;                                                                          \
-    const dim3 grid(B * a.ntr * a.ntc);                                                                          \
-    if (multi) mid_launch<T, true>(k_mg_mid_down<T, true, 1>, k_mg_mid_down<T, true, 2>,                       \
-                                   k_mg_mid_down<T, true, 3>, k_mg_mid_down<T, true, 4>, k, grid, stream, a);     \
-    else mid_launch<T, false>(k_mg_mid_down<T, false, 1>, k_mg_mid_down<T, false, 2>,                             \
-                              k_mg_mid_down<T, false, 3>, k_mg_mid_down<T, false, 4>, k, grid, stream, a);        \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }                                                                                                              \
-  extern "C" int fea_mg_mid_down_gathered_##SUF(const T* const* f, const uint8_t* const* pid, int k, int B, int H, \
-                                                int W, const T* ktab, const T* omd, int ntab, const T* rtab,      \
-                                                int nrtab, T w0, int TR, int TC, const T* gsrc, int Pr, int Pc,    \
-                                                int gcr, int gcc, void* stream) {                                 \
-    MidArgs<T> a = {};                                                                                           \
-    if (!f || !ktab || !omd || !rtab || !gsrc || ntab < 1 || ntab > FEA_MAX_PATTERNS) return FEA_EINVAL;       \
-    if (Pr < 1 || Pc < 1 || gcr < 1 || gcc < 1 || H - 1 != Pr * gcr || W - 1 != Pc * gcc) return FEA_EINVAL;    \
-    const bool multi = ntab > 1;                                                                                 \
-    if ((multi && (!pid || nrtab != ntab)) || (!multi && nrtab != 1)) return FEA_EINVAL;                        \
-    if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;                                                   \
-    if (mid_down_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;                       \
-    for (int j = 0; j <= k; ++j) {                                                                               \
-      if (!f[j] || (multi && j < k && !pid[j])) return FEA_EINVAL;                                              \
-      a.f[j] = f[j];                                                                                             \
-      a.fo[j] = const_cast<T*>(f[j]);                                                                            \
-      a.pid[j] = multi && j < k ? pid[j] : nullptr;                                                              \
-    }                                                                                                            \
-    a.ktab = ktab; a.omd = omd; a.xtab = rtab; a.w = w0; a.ntab = ntab; a.nx = nrtab;                           \
-    a.gsrc = gsrc; a.gB = B; a.gPc = Pc; a.gcr = gcr; a.gcc = gcc;                                               \
-    a.ntr = (a.H[k] - 2 + TR - 1) / TR;                                                                          \
-    a.ntc = (a.W[k] - 2 + TC - 1) / TC;                                                                          \
-    const dim3 grid(B * a.ntr * a.ntc);                                                                          \
-    if (multi) mid_launch<T, true>(k_mg_mid_down<T, true, 1, true>, k_mg_mid_down<T, true, 2, true>,           \
-                                   k_mg_mid_down<T, true, 3, true>, k_mg_mid_down<T, true, 4, true>, k, grid,     \
-                                   stream, a);                                                                    \
-    else mid_launch<T, false>(k_mg_mid_down<T, false, 1, true>, k_mg_mid_down<T, false, 2, true>,                 \
-                              k_mg_mid_down<T, false, 3, true>, k_mg_mid_down<T, false, 4, true>, k, grid,        \
-                              stream, a);                                                                         \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }                                                                                                              \
-  extern "C" int fea_mg_mid_up_##SUF(const T* const* f, const T* e, T* out, const uint8_t* const* pid, int k,   \
-                                     int B, int H, int W, const T* ktab, const T* omd, int ntab, const T* ptab,  \
-                                     int nptab, T w1, int TR, int TC, void* stream) {                            \
-    MidArgs<T> a = {};                                                                                           \
-    if (!f || !e || !out || !ktab || !omd || !ptab || ntab < 1 || ntab > FEA_MAX_PATTERNS) return FEA_EINVAL;  \
-    const bool multi = ntab > 1;                                                                                 \
-    if ((multi && (!pid || nptab != ntab)) || (!multi && nptab != 1)) return FEA_EINVAL;                        \
-    if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;                                                   \
-    if (mid_up_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;                         \
-    for (int j = 0; j <= k; ++j) {                                                                               \
-      if ((j < k && (!f[j] || f[j] == out)) || (multi && !pid[j])) return FEA_EINVAL;                           \
-      a.f[j] = j < k ? f[j] : nullptr;                                                                           \
-      a.pid[j] = multi ? pid[j] : nullptr;                                                                       \
-    }                                                                                                            \
-    if (e == out) return FEA_EINVAL;                                                                             \
-    a.e = e; a.out = out;                                                                                        \
-    a.ktab = ktab; a.omd = omd; a.xtab = ptab; a.w = w1; a.ntab = ntab; a.nx = nptab;                           \
-    a.ntr = (a.H[0] - 2 + TR - 1) / TR;                                                                          \
-    a.ntc = (a.W[0] - 2 + TC - 1) / TC;                                                                          \
-    const dim3 grid(B * a.ntr * a.ntc);                                                                          \
-    if (multi) mid_launch<T, true>(k_mg_mid_up<T, true, 1>, k_mg_mid_up<T, true, 2>, k_mg_mid_up<T, true, 3>,     \
-                                   k_mg_mid_up<T, true, 4>, k, grid, stream, a);                                  \
-    else mid_launch<T, false>(k_mg_mid_up<T, false, 1>, k_mg_mid_up<T, false, 2>, k_mg_mid_up<T, false, 3>,      \
-                              k_mg_mid_up<T, false, 4>, k, grid, stream, a);                                      \
-    FEA_LAUNCH_CHECK();                                                                                          \
+// fea_mg_mid_down and (GATHER) fea_mg_mid_down_gathered, whose finest right-hand side is read from the all-gather's
+// receive buffer gsrc: Pr x Pc blocks of gcr x gcc cells
+template <typename T, bool GATHER>
+static int mid_down(const T* const* f, const uint8_t* const* pid, int k, int B, int H, int W, const T* ktab,
+                    const T* omd, int ntab, const T* rtab, int nrtab, T w0, int TR, int TC, const T* gsrc, int Pr,
+                    int Pc, int gcr, int gcc, void* stream) {
+  MidArgs<T> a = {};
+  if (!f || !omd || !rtab || !tab_ok(ktab, ntab, pid) || !xtab_ok(nrtab, ntab)) return FEA_EINVAL;
+  if (GATHER && (!gsrc || Pr < 1 || Pc < 1 || gcr < 1 || gcc < 1 || H - 1 != Pr * gcr || W - 1 != Pc * gcc))
+    return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;
+  if (mid_down_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;
+  for (int j = 0; j <= k; ++j) {
+    if (!f[j] || (multi && j < k && !pid[j])) return FEA_EINVAL;
+    a.f[j] = f[j];
+    a.fo[j] = const_cast<T*>(f[j]);
+    a.pid[j] = multi && j < k ? pid[j] : nullptr;
   }
+  a.ktab = ktab; a.omd = omd; a.xtab = rtab; a.w = w0; a.ntab = ntab; a.nx = nrtab;
+  if (GATHER) {
+    a.gsrc = gsrc; a.gB = B; a.gPc = Pc; a.gcr = gcr; a.gcc = gcc;
+  }
+  a.ntr = (a.H[k] - 2 + TR - 1) / TR;
+  a.ntc = (a.W[k] - 2 + TC - 1) / TC;
+  const dim3 grid(B * a.ntr * a.ntc);
+  if (multi) mid_launch<T, true>(k_mg_mid_down<T, true, 1, GATHER>, k_mg_mid_down<T, true, 2, GATHER>,
+                                 k_mg_mid_down<T, true, 3, GATHER>, k_mg_mid_down<T, true, 4, GATHER>, k, grid,
+                                 stream, a);
+  else mid_launch<T, false>(k_mg_mid_down<T, false, 1, GATHER>, k_mg_mid_down<T, false, 2, GATHER>,
+                            k_mg_mid_down<T, false, 3, GATHER>, k_mg_mid_down<T, false, 4, GATHER>, k, grid,
+                            stream, a);
+  return launch_status();
+}
 
+template <typename T>
+static int mid_up(const T* const* f, const T* e, T* out, const uint8_t* const* pid, int k, int B, int H, int W,
+                  const T* ktab, const T* omd, int ntab, const T* ptab, int nptab, T w1, int TR, int TC,
+                  void* stream) {
+  MidArgs<T> a = {};
+  if (!f || !e || !out || !omd || !ptab || !tab_ok(ktab, ntab, pid) || !xtab_ok(nptab, ntab)) return FEA_EINVAL;
+  const bool multi = ntab > 1;
+  if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;
+  if (mid_up_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;
+  for (int j = 0; j <= k; ++j) {
+    if ((j < k && (!f[j] || f[j] == out)) || (multi && !pid[j])) return FEA_EINVAL;
+    a.f[j] = j < k ? f[j] : nullptr;
+    a.pid[j] = multi ? pid[j] : nullptr;
+  }
+  if (e == out) return FEA_EINVAL;
+  a.e = e; a.out = out;
+  a.ktab = ktab; a.omd = omd; a.xtab = ptab; a.w = w1; a.ntab = ntab; a.nx = nptab;
+  a.ntr = (a.H[0] - 2 + TR - 1) / TR;
+  a.ntc = (a.W[0] - 2 + TC - 1) / TC;
+  const dim3 grid(B * a.ntr * a.ntc);
+  if (multi) mid_launch<T, true>(k_mg_mid_up<T, true, 1>, k_mg_mid_up<T, true, 2>, k_mg_mid_up<T, true, 3>,
+                                 k_mg_mid_up<T, true, 4>, k, grid, stream, a);
+  else mid_launch<T, false>(k_mg_mid_up<T, false, 1>, k_mg_mid_up<T, false, 2>, k_mg_mid_up<T, false, 3>,
+                            k_mg_mid_up<T, false, 4>, k, grid, stream, a);
+  return launch_status();
+}
+
+#define FEA_MID_API(SUF, T)                                                                                        \
+  extern "C" int fea_mg_mid_down_##SUF(const T* const* f, const uint8_t* const* pid, int k, int B, int H, int W,    \
+                                       const T* ktab, const T* omd, int ntab, const T* rtab, int nrtab, T w0,       \
+                                       int TR, int TC, void* stream) {                                             \
+    return mid_down<T, false>(f, pid, k, B, H, W, ktab, omd, ntab, rtab, nrtab, w0, TR, TC, nullptr, 0, 0, 0, 0,    \
+                              stream);                                                                             \
+  }                                                                                                                \
+  extern "C" int fea_mg_mid_down_gathered_##SUF(const T* const* f, const uint8_t* const* pid, int k, int B, int H,  \
+                                                int W, const T* ktab, const T* omd, int ntab, const T* rtab,        \
+                                                int nrtab, T w0, int TR, int TC, const T* gsrc, int Pr, int Pc,     \
+                                                int gcr, int gcc, void* stream) {                                  \
+    return mid_down<T, true>(f, pid, k, B, H, W, ktab, omd, ntab, rtab, nrtab, w0, TR, TC, gsrc, Pr, Pc, gcr, gcc,  \
+                             stream);                                                                              \
+  }                                                                                                                \
+  extern "C" int fea_mg_mid_up_##SUF(const T* const* f, const T* e, T* out, const uint8_t* const* pid, int k,      \
+                                     int B, int H, int W, const T* ktab, const T* omd, int ntab, const T* ptab,     \
+                                     int nptab, T w1, int TR, int TC, void* stream) {                              \
+    return mid_up<T>(f, e, out, pid, k, B, H, W, ktab, omd, ntab, ptab, nptab, w1, TR, TC, stream);                \
+  }
 FEA_MID_API(f32, float)
 FEA_MID_API(f64, double)
 

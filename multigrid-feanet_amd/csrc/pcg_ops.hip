@@ -381,10 +381,6 @@ static PcgArgs<T> pcg_args(int H, int W, int ld, long long bs) {
   return g;
 }
 
-static inline bool pcg_tab_ok(const void* ktab, int ntab, const void* pid) {
-  return ktab && ntab >= 1 && ntab <= FEA_MAX_PATTERNS && (ntab == 1 || pid);
-}
-
 template <typename T>
 static inline bool pcg_nt(int B, long long bs) { return (long long)B * bs * (long long)sizeof(T) > nt_bytes(); }
 
@@ -402,7 +398,7 @@ extern "C" int fea_pcg_scalar_step(const double* part, long long per, double* sc
       step > FEA_PCG_STEP_RR)
     return FEA_EINVAL;
   k_pcg_scalar<<<B, 256, 0, (hipStream_t)stream>>>(part, per, scalars, hist, hist_rows, B, step);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
 template <typename T, int MODE, bool MIX = false>
@@ -419,49 +415,71 @@ static void pcg_launch(const PcgArgs<T>& g, int B, void* stream) {
   }
 }
 
-#define FEA_PCG_API(SUF, T)                                                                                      \
-  extern "C" int fea_pcg_residual_##SUF(const T* x, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab, \
-                                        double* part, int B, int H, int W, int ld, long long bs, void* stream) {  \
-    if (!x || !f || !r || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) || !pcg_tab_ok(ktab, ntab, pid) ||       \
-        r == x)                                                                                                  \
-      return FEA_EINVAL;                                                                                         \
-    PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);                                                                    \
-    g.v = x; g.f = f; g.out = r; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.part = part;                       \
-    pcg_launch<T, kPcgResidual>(g, B, stream);                                                                   \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }                                                                                                              \
-  extern "C" int fea_pcg_direction_##SUF(const T* z, const T* p_in, T* p_out, const uint8_t* pid, const T* ktab,  \
-                                         int ntab, const double* scalars, double* part, int B, int H, int W,     \
-                                         int ld, long long bs, void* stream) {                                   \
-    if (!z || !p_in || !p_out || !scalars || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) ||                   \
-        !pcg_tab_ok(ktab, ntab, pid) || p_out == p_in || p_out == z)                                             \
-      return FEA_EINVAL;                                                                                         \
-    PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);                                                                    \
-    g.v = z; g.v2 = p_in; g.out = p_out; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars;              \
-    g.part = part;                                                                                               \
-    pcg_launch<T, kPcgDirection>(g, B, stream);                                                                  \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }                                                                                                              \
-  extern "C" int fea_pcg_update_##SUF(const T* p, T* x, T* r, const uint8_t* pid, const T* ktab, int ntab,        \
-                                      const double* scalars, double* part, int B, int H, int W, int ld,          \
-                                      long long bs, void* stream) {                                              \
-    if (!p || !x || !r || !scalars || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) ||                          \
-        !pcg_tab_ok(ktab, ntab, pid) || x == p || r == p || x == r)                                              \
-      return FEA_EINVAL;                                                                                         \
-    PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);                                                                    \
-    g.v = p; g.x = x; g.r = r; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars; g.part = part;         \
-    pcg_launch<T, kPcgUpdate>(g, B, stream);                                                                     \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }                                                                                                              \
-  extern "C" int fea_pcg_dot_##SUF(const T* r, const T* z, double* part, int B, int H, int W, int ld,            \
-                                   long long bs, void* stream) {                                                 \
-    if (!r || !z || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;                           \
-    PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);                                                                    \
-    g.v = r; g.v2 = z; g.part = part;                                                                            \
-    k_pcg_dot<T><<<mg_grid(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(g);                              \
-    FEA_LAUNCH_CHECK();                                                                                          \
-  }
+template <typename T>
+static int pcg_residual(const T* x, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab, double* part, int B,
+                        int H, int W, int ld, long long bs, void* stream) {
+  if (!x || !f || !r || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) || !tab_ok(ktab, ntab, pid) || r == x)
+    return FEA_EINVAL;
+  PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);
+  g.v = x; g.f = f; g.out = r; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.part = part;
+  pcg_launch<T, kPcgResidual>(g, B, stream);
+  return launch_status();
+}
 
+template <typename T>
+static int pcg_direction(const T* z, const T* p_in, T* p_out, const uint8_t* pid, const T* ktab, int ntab,
+                         const double* scalars, double* part, int B, int H, int W, int ld, long long bs,
+                         void* stream) {
+  if (!z || !p_in || !p_out || !scalars || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) ||
+      !tab_ok(ktab, ntab, pid) || p_out == p_in || p_out == z)
+    return FEA_EINVAL;
+  PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);
+  g.v = z; g.v2 = p_in; g.out = p_out; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars;
+  g.part = part;
+  pcg_launch<T, kPcgDirection>(g, B, stream);
+  return launch_status();
+}
+
+template <typename T>
+static int pcg_update(const T* p, T* x, T* r, const uint8_t* pid, const T* ktab, int ntab, const double* scalars,
+                      double* part, int B, int H, int W, int ld, long long bs, void* stream) {
+  if (!p || !x || !r || !scalars || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs) || !tab_ok(ktab, ntab, pid) ||
+      x == p || r == p || x == r)
+    return FEA_EINVAL;
+  PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);
+  g.v = p; g.x = x; g.r = r; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars; g.part = part;
+  pcg_launch<T, kPcgUpdate>(g, B, stream);
+  return launch_status();
+}
+
+template <typename T>
+static int pcg_dot(const T* r, const T* z, double* part, int B, int H, int W, int ld, long long bs, void* stream) {
+  if (!r || !z || !part || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
+  PcgArgs<T> g = pcg_args<T>(H, W, ld, bs);
+  g.v = r; g.v2 = z; g.part = part;
+  k_pcg_dot<T><<<mg_grid(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(g);
+  return launch_status();
+}
+
+#define FEA_PCG_API(SUF, T)                                                                                        \
+  extern "C" int fea_pcg_residual_##SUF(const T* x, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab,   \
+                                        double* part, int B, int H, int W, int ld, long long bs, void* stream) {    \
+    return pcg_residual<T>(x, f, r, pid, ktab, ntab, part, B, H, W, ld, bs, stream);                               \
+  }                                                                                                                \
+  extern "C" int fea_pcg_direction_##SUF(const T* z, const T* p_in, T* p_out, const uint8_t* pid, const T* ktab,    \
+                                         int ntab, const double* scalars, double* part, int B, int H, int W,       \
+                                         int ld, long long bs, void* stream) {                                     \
+    return pcg_direction<T>(z, p_in, p_out, pid, ktab, ntab, scalars, part, B, H, W, ld, bs, stream);               \
+  }                                                                                                                \
+  extern "C" int fea_pcg_update_##SUF(const T* p, T* x, T* r, const uint8_t* pid, const T* ktab, int ntab,          \
+                                      const double* scalars, double* part, int B, int H, int W, int ld,            \
+                                      long long bs, void* stream) {                                                \
+    return pcg_update<T>(p, x, r, pid, ktab, ntab, scalars, part, B, H, W, ld, bs, stream);                        \
+  }                                                                                                                \
+  extern "C" int fea_pcg_dot_##SUF(const T* r, const T* z, double* part, int B, int H, int W, int ld,              \
+                                   long long bs, void* stream) {                                                   \
+    return pcg_dot<T>(r, z, part, B, H, W, ld, bs, stream);                                                        \
+  }
 FEA_PCG_API(f32, float)
 FEA_PCG_API(f64, double)
 
@@ -489,7 +507,7 @@ extern "C" int fea_pcg_narrow_f64f32(const double* r, float* r32, const double* 
   const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
   if (pcg_nt<double>(B, bs)) k_pcg_narrow<true><<<grid, 256, 0, (hipStream_t)stream>>>(g);
   else k_pcg_narrow<false><<<grid, 256, 0, (hipStream_t)stream>>>(g);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
 extern "C" int fea_pcg_dot_f64f32(const double* r, const float* z32, double* part, int B, int H, int W, int ld,
@@ -498,20 +516,20 @@ extern "C" int fea_pcg_dot_f64f32(const double* r, const float* z32, double* par
   PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
   g.v = r; g.z32 = z32; g.part = part;
   k_pcg_dot<double, float><<<mg_grid(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(g);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
 extern "C" int fea_pcg_direction_f64f32(const float* z32, const double* p_in, double* p_out, const uint8_t* pid,
                                         const double* ktab, int ntab, const double* scalars, double* part, int B,
                                         int H, int W, int ld, long long bs, int ld32, long long bs32, void* stream) {
   if (!z32 || !p_in || !p_out || !scalars || !part || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32) ||
-      !pcg_tab_ok(ktab, ntab, pid) || p_out == p_in || (const void*)p_out == (const void*)z32)
+      !tab_ok(ktab, ntab, pid) || p_out == p_in || (const void*)p_out == (const void*)z32)
     return FEA_EINVAL;
   PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
   g.z32 = z32; g.v2 = p_in; g.out = p_out; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars;
   g.part = part;
   pcg_launch<double, kPcgDirection, true>(g, B, stream);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
 
 extern "C" int fea_pcg_update_f64f32(const double* p, double* x, double* r, float* r32, const uint8_t* pid,
@@ -520,11 +538,11 @@ extern "C" int fea_pcg_update_f64f32(const double* p, double* x, double* r, floa
                                      long long bs32, void* stream) {
   const void* n = r32;
   if (!p || !x || !r || !r32 || !scalars || !sb || !part || !pcg_mix_ok(B, H, W, ld, bs, ld32, bs32) ||
-      !pcg_tab_ok(ktab, ntab, pid) || x == p || r == p || x == r || n == p || n == x || n == r)
+      !tab_ok(ktab, ntab, pid) || x == p || r == p || x == r || n == p || n == x || n == r)
     return FEA_EINVAL;
   PcgArgs<double> g = pcg_mix_args(H, W, ld, bs, ld32, bs32);
   g.v = p; g.x = x; g.r = r; g.r32 = r32; g.pid = pid; g.ktab = ktab; g.ntab = ntab; g.sc = scalars; g.sb = sb;
   g.part = part;
   pcg_launch<double, kPcgUpdate, true>(g, B, stream);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }

@@ -60,5 +60,5 @@ using namespace fea;
 extern "C" int fea_interface_pattern_map(uint8_t* out, long long ld, int N, int shape, double size, void* stream) {
   if (!out || N < 2 || N > (1 << 20) + 1 || ld < N || (shape != 0 && shape != 1) || !(size > 0)) return FEA_EINVAL;
   k_interface_pattern_map<<<dim3((N + 255) / 256, N), 256, 0, (hipStream_t)stream>>>(out, ld, N, shape, size / 2);
-  FEA_LAUNCH_CHECK();
+  return launch_status();
 }
