@@ -203,6 +203,18 @@ size_t fea_transfer_weight_grad_ws_bytes_f64(int C, int B, int Hc, int Wc);
  *     Two-material stencils (ntab > 1): each node's stiffness weights are read from its own pattern's row with
  *     mirrored taps (ktab[p(i)][8-t] for tap t), which equals KNet's ktab[p(i+t)][t] (FEANet/model.py:22-30) bit for
  *     bit when K is a symmetric FE stiffness (stencil_table(); feanet_amd.mesh_setup.stencil_mirror_mismatches).
+ *
+ *     Write sets (tests/footprint.py pins them over the whole allocation).  A field output is written on the interior
+ *     nodes of its level and nowhere else, unless its entry point says otherwise (fea_mg_pack: all H x W nodes; the
+ *     *_send buffers: the block's nodes inside the output level's interior; fea_mg_cycle_join_rects: the rectangles'
+ *     fine and coarse nodes): boundary nodes, the ghost ring, pad columns, the rows between samples and whatever lies
+ *     behind the last sample are never stored to, and no input is modified.  Every kernel LOADS from that storage
+ *     (a strip's last vectors reach past column W, row loads are clamped onto the ghost rows) and keeps it out of its
+ *     results with selects, so results do not depend on what it holds, with one exception: fea_mg_cycle_join and
+ *     fea_mg_cycle_join_rects (below) need finite values there.
+ *     Norm workspaces: a call with norm_ws / ws writes nowhere but inside fea_norm_workspace_bytes(B, H, W) of it;
+ *     the deferred cycle join writes exactly B * fea_mg_join_norm_parts doubles.  An appended norm writes row cnt[1]
+ *     of the history (B doubles) and cnt[1], nothing else.
  * ------------------------------------------------------------------------- */
 
 /* contiguous [B,1,H,W] -> framed, applying u*geo + bc (src NULL: u = 0; geo NULL: the square geometry,
@@ -333,7 +345,13 @@ int fea_mg_prolong2_f64(const double* fc, const double* ec2, const double* f, do
  * anyway: appended as row norm_cnt[1] of norm_hist (B doubles per row; norm_cnt[1] += 1; norm_cnt[0]
  * unused), reduced deterministically by a one-workgroup kernel launched after the join on the same
  * stream; norm_ws >= fea_norm_workspace_bytes(B, H, W).  Replaces the per-cycle residual pass of the driver
- * loops (M-FEANet-mg_test.ipynb:27426-27436). */
+ * loops (M-FEANet-mg_test.ipynb:27426-27436).
+ * Requirement on non-node storage: the join (and fea_mg_cycle_join_rects) keeps a boundary node's value through a
+ * zero omega/d, v = 0 * (f - K x) + x, where K x at a boundary node reads the ghost ring and the pad columns next to
+ * it.  The frames of u, f and ec (all B * bstride elements: ghost ring, pad columns, rows between samples) must
+ * therefore hold FINITE values; which ones does not matter.  Zeroed allocations satisfy this and stay so, because
+ * no mg kernel stores outside the nodes (feanet_amd.solver._Level allocates zeros).  Elements behind the last
+ * sample are free. */
 int fea_mg_cycle_join_f32(const float* u, const float* ec, const float* f, float* u_out, float* fc,
                           const uint8_t* pid, const uint8_t* pidc, const float* ktab, const float* omd, int ntab,
                           const float* ptab, int nptab, const float* rtab, int nrtab, float w1, float w0, int B,
@@ -386,7 +404,9 @@ int fea_mg_residual_norm_f64(const double* u, const double* f, const uint8_t* pi
  * padding; nlayers <= 3), g = interior mask.  u == NULL: zero initial guess (coarse levels).
  * u_raw (optional, framed like u): the iterate as the caller passed it before reset_boundary — the
  * reference forms j - u with the un-reset u, so a first sweep from a guess whose boundary is not the
- * Dirichlet data sees (bc - u_raw) on the boundary nodes; NULL = u already holds the boundary. */
+ * Dirichlet data sees (bc - u_raw) on the boundary nodes; NULL = u already holds the boundary.
+ * Write set: the interior nodes of out; its boundary nodes are neither written nor read (boundary values come from
+ * u, zero for u == NULL). */
 int fea_mg_hsweep_f32(const float* u, const float* u_raw, const float* f, float* out, const uint8_t* pid,
                       const float* ktab, const float* omd, int ntab, const float* hw, int nlayers, int B, int H,
                       int W, int ld, long long bstride, void* stream);
@@ -399,7 +419,9 @@ int fea_mg_hsweep_f64(const double* u, const double* u_raw, const double* f, dou
  *   fc = w0 R(f - K out) on the (H+1)/2 x (W+1)/2 level (framed ldc, bsc) as fea_mg_residual_restrict with a
  *   stored iterate.  prolong_hsweep: x = u + w1 P(ec) on the interior (fea_mg_prolong_add, ec = the coarse
  *   correction), then out = HRelax(x); u_raw as for fea_mg_hsweep (the first sweep of a cycle after a load with
- *   no pre-sweep sees the un-reset guess on the boundary).  Both bitwise the two launches they replace; H, W odd; out != u. */
+ *   no pre-sweep sees the un-reset guess on the boundary).  Both bitwise the two launches they replace; H, W odd; out != u.
+ *   Write sets: the interior nodes of out, and (hsweep_restrict) the interior nodes of fc.  out's boundary nodes are
+ *   neither written nor read: the residual of hsweep_restrict takes the boundary values from u (zero for u == NULL). */
 int fea_mg_hsweep_restrict_f32(const float* u, const float* u_raw, const float* f, float* out, float* fc,
                                const uint8_t* pid, const float* ktab, const float* omd, int ntab, const float* hw,
                                int nlayers, const float* rtab, int nrtab, float w0, int B, int H, int W, int ld,
@@ -475,7 +497,8 @@ size_t fea_mg_hjac_tail_lds_bytes(int Ht, int Wt, int nlev, int elem_size, int m
  *   reads f[0] = f_a, writes f[1..k] = f_{a+1} .. f_{a+k} (interior).  Tile TR x TC of level a+k.
  * mid_up: the prolongation + correction + post-sweep of levels a+k-1 .. a from e = u_{a+k}
  *   (:177-181, one fea_mg_prolong_sweep(u = NULL) per level): reads f[0..k-1] = f_a .. f_{a+k-1},
- *   writes out = u_a (interior); intermediate iterates are not stored.  Tile TR x TC of level a.
+ *   writes out = u_a (interior nodes only: the boundary nodes of out are not written, and taken as zero, as
+ *   in every level below the finest); intermediate iterates are not stored.  Tile TR x TC of level a.
  * Both return FEA_EINVAL if the tile's LDS footprint (fea_mg_mid_lds_bytes) does not fit. */
 int fea_mg_mid_down_f32(const float* const* f, const uint8_t* const* pid, int k, int B, int H, int W,
                         const float* ktab, const float* omd, int ntab, const float* rtab, int nrtab, float w0,
@@ -561,6 +584,9 @@ int fea_interface_pattern_map(uint8_t* out, long long ld, int N, int shape, doub
  *     Every kernel also writes one partial sum per wave, in double, to part[b * fea_pcg_parts(H, W, elem) + i];
  *     fea_pcg_scalar_step sums a sample's partials in index order (no atomics, the same order every launch and for
  *     every batch size) and advances the sample's scalar block.  Nothing allocates or synchronises.
+ *     Write sets: exactly B * fea_pcg_parts doubles of part; field outputs as stated per function, never the ghost
+ *     ring, pad columns or anything behind the last sample; inputs are not modified.  Pad columns and the storage
+ *     behind the last sample may hold anything (the results do not depend on them).
  *
  *     Scalar block: FEA_PCG_NSCALARS doubles per sample.  The caller sets EPS and RTOL before FEA_PCG_STEP_INIT
  *     (RTOL < 0: the threshold is EPS, absolute; RTOL >= 0: RTOL * ||r0||); the steps own the rest.
@@ -602,7 +628,9 @@ int fea_pcg_residual_f32(const float* x, const float* f, float* r, const uint8_t
 int fea_pcg_residual_f64(const double* x, const double* f, double* r, const uint8_t* pid, const double* ktab, int ntab,
                          double* part, int B, int H, int W, int ld, long long bstride, void* stream);
 /* p_out = z + beta p_in on the interior (beta = scalars[b][FEA_PCG_BETA], applied in T); partials of p_out.K p_out.
- * Every strip rebuilds the new direction on its halo from z and p_in, so p_out must not be p_in (nor z): p ping-pongs. */
+ * Every strip rebuilds the new direction on its halo from z and p_in, so p_out must not be p_in (nor z): p ping-pongs.
+ * Only interior nodes of p_out are written: its boundary nodes and ghost ring are left as they are, and the caller
+ * keeps them zero (both p buffers start zeroed and no kernel stores there). */
 int fea_pcg_direction_f32(const float* z, const float* p_in, float* p_out, const uint8_t* pid, const float* ktab,
                           int ntab, const double* scalars, double* part, int B, int H, int W, int ld,
                           long long bstride, void* stream);

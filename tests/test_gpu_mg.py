@@ -55,6 +55,9 @@ class Frame:
             self.pid_np = oracle_maps().get(self.N) if self.N == self.H else None
             if self.pid_np is None:
                 self.pid_np = ms.interface_pattern_map(self.N)
+            if self.H != self.N:  # a rectangle: the centred row crop of the square's map (as test_gpu_pcg.py)
+                r0 = (self.N - self.H) // 2
+                self.pid_np = np.ascontiguousarray(self.pid_np[r0:r0 + self.H])
         else:
             self.pid_np = np.zeros((self.H, self.W), np.uint8)
         self.L = _Level(m, n, B, T, torch.device("cuda"), self.pid_np if problem == "interface" else None)
@@ -609,6 +612,110 @@ def test_mg_rect_kernels(T, m, n, B):
     for lo, hi in ((0, 0), (1, H - 1), (2, max(2, H // 2)), (H // 2, H - 1), (3, 3)):
         for clo, chi in ((0, 0), (1, W - 1), (2, max(2, W // 2)), (W // 3, W - 1)):
             _lib.call("mg_residual_norm", T, fr.L.a.data_ptr(), fr.L.f.data_ptr(), None, kt.data_ptr(), 1,
+                      res.data_ptr(), ws.data_ptr(), *fr.args(), lo, hi, clo, chi, None)
+            a, b = (1, H - 1) if (lo, hi) == (0, 0) else (lo, hi)
+            c, d = (1, W - 1) if (clo, chi) == (0, 0) else (clo, chi)
+            ref = np.sqrt((r[:, a:b, c:d].astype(np.float64) ** 2).sum(axis=(1, 2)))
+            np.testing.assert_allclose(res.cpu().numpy(), ref, rtol=1e-5 if T == torch.float32 else 1e-12,
+                                       err_msg=f"norm rows {lo}:{hi} cols {clo}:{chi}")
+
+
+# Widths that are not 2^k + 1.  321: three fp64 / two fp32 strips, the last one partial and ending in mid-wave
+# (the row's last vector in lane 31 / 15); 323 = 3 (mod 4): one valid element in the fp32 tail vector.
+ODD_WIDTHS = [(33, 321, 2), (35, 323, 3)]
+
+
+@pytest.mark.parametrize("T", [torch.float32, torch.float64])
+@pytest.mark.parametrize("problem", ["poisson", "interface"])
+@pytest.mark.parametrize("H,W,B", ODD_WIDTHS)
+def test_mg_kernels_odd_widths(T, problem, H, W, B, nt):
+    """The value comparisons of test_mg_sweep / test_mg_transfer / test_mg_rect_kernels against the oracle at
+    33 x 321 and 35 x 323, Poisson and two-material (distinct per-pattern R / P), same tolerances: mg_sweep (both
+    modes), mg_residual_restrict (three modes), mg_sweep_restrict, mg_prolong_sweep, mg_prolong_add, and
+    mg_residual_norm over row and column ranges."""
+    from feanet_amd import _lib
+    rng = np.random.default_rng(H + W + B)
+    fr = Frame(W - 1, B, T, problem, m=H - 1)
+    co = Frame((W - 1) // 2, B, T, problem, m=(H - 1) // 2)
+    assert fr.pid_np.shape == (H, W) and co.pid_np.shape == (co.H, co.W)
+    ktab, omd, R, P, kt, om, rt, pt = tables(problem, T, learned=(problem == "interface"))
+    ntab = ktab.shape[0]
+    u, f = rand_state(rng, B, (H, W), T)
+    geo, _ = orc.square_geometry((H, W), npdt(T))
+    pid = fr.pid_np.astype(np.int64)
+    w0, w1 = 1.25, 0.75
+    fr.put("a", u)
+    fr.put("f", f)
+
+    def untouched(out, what):
+        assert (out[:, 0, :] == 7).all() and (out[:, -1, :] == 7).all() and (out[:, :, 0] == 7).all() and \
+            (out[:, :, -1] == 7).all(), f"{what}: boundary written"
+    # sweep, with an iterate and from a zero guess
+    fr.put("b", u * 0 + 7.0)
+    _lib.call("mg_sweep", T, fr.L.a.data_ptr(), fr.L.f.data_ptr(), fr.L.b.data_ptr(), fr.pid(), kt.data_ptr(),
+              om.data_ptr(), ntab, *fr.args(), None)
+    up = orc.jacobi_sweep(u, f, fr.pid_np, ktab, geo, u * (1 - geo))
+    out = fr.get("b")
+    close(out[:, 1:-1, 1:-1], up[:, 1:-1, 1:-1], T, "sweep")
+    untouched(out, "sweep")
+    _lib.call("mg_sweep", T, None, fr.L.f.data_ptr(), fr.L.b.data_ptr(), fr.pid(), kt.data_ptr(), om.data_ptr(), ntab,
+              *fr.args(), None)
+    out = fr.get("b")
+    close(out[:, 1:-1, 1:-1], (omd[pid] * f)[:, 1:-1, 1:-1], T, "zero sweep")
+    untouched(out, "zero sweep")
+    # residual + restriction of a stored iterate
+    _lib.call("mg_residual_restrict", T, fr.L.a.data_ptr(), fr.L.f.data_ptr(), None, co.L.f.data_ptr(), fr.pid(),
+              kt.data_ptr(), om.data_ptr(), ntab, rt.data_ptr(), ntab, w0, *fr.args(), co.L.ld, co.L.bs, None)
+    close(co.get("f"), orc.restrict(f - orc.knet_apply(u, fr.pid_np, ktab), fr.pid_np, R, w0), T, "RR")
+    # fused pre-sweep + residual + restriction
+    fr.put("b", u * 0 + 7.0)
+    _lib.call("mg_sweep_restrict", T, fr.L.a.data_ptr(), fr.L.f.data_ptr(), fr.L.b.data_ptr(), co.L.f.data_ptr(),
+              fr.pid(), kt.data_ptr(), om.data_ptr(), ntab, rt.data_ptr(), ntab, w0, *fr.args(), co.L.ld, co.L.bs,
+              None, None, None, None)
+    out = fr.get("b")
+    close(out[:, 1:-1, 1:-1], up[:, 1:-1, 1:-1], T, "fused sweep u'")
+    untouched(out, "fused sweep")
+    close(co.get("f"), orc.restrict(f - orc.knet_apply(up, fr.pid_np, ktab), fr.pid_np, R, w0), T, "fused RR")
+    # zero guess, v stored; then v not stored
+    v = omd[pid] * f * geo
+    fc_ref = orc.restrict(f - orc.knet_apply(v, fr.pid_np, ktab), fr.pid_np, R, w0)
+    fr.put("b", u * 0)
+    _lib.call("mg_residual_restrict", T, None, fr.L.f.data_ptr(), fr.L.b.data_ptr(), co.L.f.data_ptr(), fr.pid(),
+              kt.data_ptr(), om.data_ptr(), ntab, rt.data_ptr(), ntab, w0, *fr.args(), co.L.ld, co.L.bs, None)
+    close(fr.get("b"), v, T, "zero-guess v")
+    close(co.get("f"), fc_ref, T, "zero RR")
+    fr.put("b", u * 0 + 7.0)
+    co.put("f", fc_ref * 0)
+    _lib.call("mg_residual_restrict", T, None, fr.L.f.data_ptr(), None, co.L.f.data_ptr(), fr.pid(),
+              kt.data_ptr(), om.data_ptr(), ntab, rt.data_ptr(), ntab, w0, *fr.args(), co.L.ld, co.L.bs, None)
+    assert (fr.get("b") == 7).all(), "v written although v_out = NULL"
+    close(co.get("f"), fc_ref, T, "zero RR, v not stored")
+    # prolongation + correction, with and without the post-sweep
+    e = rng.standard_normal((B, co.H, co.W)).astype(npdt(T))
+    e[:, 0, :] = e[:, -1, :] = e[:, :, 0] = e[:, :, -1] = 0
+    co.put("a", e)
+    x = u + orc.prolong(e, co.pid_np, P, w1)
+    fr.put("b", u * 0 + 7.0)
+    _lib.call("mg_prolong_sweep", T, fr.L.a.data_ptr(), co.L.a.data_ptr(), fr.L.f.data_ptr(), fr.L.b.data_ptr(),
+              fr.pid(), co.pid(), kt.data_ptr(), om.data_ptr(), ntab, pt.data_ptr(), ntab, w1, *fr.args(), co.L.ld,
+              co.L.bs, None)
+    out = fr.get("b")
+    close(out[:, 1:-1, 1:-1], orc.jacobi_sweep(x, f, fr.pid_np, ktab, geo, u * (1 - geo))[:, 1:-1, 1:-1], T,
+          "prolong+sweep")
+    untouched(out, "prolong+sweep")
+    fr.put("b", u * 0 + 7.0)
+    _lib.call("mg_prolong_add", T, fr.L.a.data_ptr(), co.L.a.data_ptr(), fr.L.b.data_ptr(), co.pid(), pt.data_ptr(),
+              ntab, w1, *fr.args(), co.L.ld, co.L.bs, None)
+    out = fr.get("b")
+    close(out[:, 1:-1, 1:-1], x[:, 1:-1, 1:-1], T, "prolong+add")
+    untouched(out, "prolong+add")
+    # residual norm over row and column ranges
+    ws = torch.zeros(_lib.norm_workspace_bytes(B, H, W) // 8 + 1, dtype=torch.float64, device="cuda")
+    res = torch.zeros(B, dtype=torch.float64, device="cuda")
+    r = f - orc.knet_apply(u, fr.pid_np, ktab)
+    for lo, hi in ((0, 0), (1, H - 1), (2, H // 2), (H // 2, H - 1), (3, 3)):
+        for clo, chi in ((0, 0), (1, W - 1), (2, W // 2), (W // 3, W - 1), (W - 2, W - 1)):
+            _lib.call("mg_residual_norm", T, fr.L.a.data_ptr(), fr.L.f.data_ptr(), fr.pid(), kt.data_ptr(), ntab,
                       res.data_ptr(), ws.data_ptr(), *fr.args(), lo, hi, clo, chi, None)
             a, b = (1, H - 1) if (lo, hi) == (0, 0) else (lo, hi)
             c, d = (1, W - 1) if (clo, chi) == (0, 0) else (clo, chi)
