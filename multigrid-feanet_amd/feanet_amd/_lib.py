@@ -21,84 +21,171 @@ LL = ctypes.c_longlong
 F32 = ctypes.c_float
 F64 = ctypes.c_double
 
-# name -> argtypes (the _f32/_f64 pairs share a signature up to the scalar type S)
+# name -> "TYPE param, ..." as declared in include/feanet_hip.h, in that order (tests/test_abi.py compares the two).
+# TYPE: P pointer, I int, LL long long, S the scalar T of the _f32/_f64 pair (which shares the signature otherwise),
+# D double, PI / PLL int* / long long* results.  `stream` is last everywhere and is not part of a launch record.
+_CTYPES = {"P": P, "I": I, "LL": LL, "S": "S", "D": F64, "PI": ctypes.POINTER(I), "PLL": ctypes.POINTER(LL)}
 _SIGS = {
-    "knet_apply": [P, P, P, P, I, I, I, I, P],
-    "split_x": [P, P, P, I, I, I, I, P],
-    "jacobi_sweep": [P, P, P, P, P, P, I, P, LL, P, LL, I, I, I, P],
-    "residual": [P, P, P, P, P, I, I, I, I, P],
-    "jacobi_sweep_pbc": [P, P, P, P, P, I, I, P],
-    "pbc_pad": [P, P, I, I, I, I, P],
-    "restrict": [P, I, P, P, P, I, "S", I, I, I, P],
-    "prolong": [P, I, P, P, P, P, I, "S", I, I, I, P],
-    "residual_norm": [P, P, P, P, I, P, P, I, I, I, P],
+    "knet_apply": "P u, P y, P pid, P ktab, I ntab, I B, I H, I W, P stream",
+    "split_x": "P x, P xs, P pid, I C, I B, I H, I W, P stream",
+    "jacobi_sweep": "P u, P f, P out, P pid, P ktab, P omd, I ntab, P geo, LL geo_bstride, P bc, LL bc_bstride, "
+                    "I B, I H, I W, P stream",
+    "residual": "P u, P f, P r, P pid, P ktab, I ntab, I B, I H, I W, P stream",
+    "jacobi_sweep_pbc": "P u, P f, P out, P ktab, P omd, I B, I N, P stream",
+    "pbc_pad": "P u, P dst, I B, I N, I lo, I hi, P stream",
+    "restrict": "P x, I C, P fc, P pid, P rtab, I ntab, S w0, I B, I H, I W, P stream",
+    "prolong": "P e, I C, P out, P add, P pidc, P ptab, I ntab, S w1, I B, I Hc, I Wc, P stream",
+    "residual_norm": "P u, P f, P pid, P ktab, I ntab, P out, P ws, I B, I H, I W, P stream",
     # adjoints (autograd)
-    "knet_apply_adj": [P, P, P, P, I, I, I, I, P],
-    "jacobi_sweep_adj": [P, P, P, P, P, P, I, P, LL, I, I, I, P],
-    "restrict_adj": [P, I, P, P, P, I, "S", I, I, I, P],
-    "prolong_adj": [P, I, P, P, P, I, "S", I, I, I, P],
-    "transfer_weight_grad": [P, I, P, I, I, I, "S", P, P, I, I, I, P],
-    "stencil_weight_grad": [P, P, P, I, "S", P, P, I, I, I, P],
-    # framed level ops: (..., B, H, W, ld, bstride[, ldc, bstridec], stream)
-    "mg_pack": [P, P, P, LL, P, LL, I, I, I, I, LL, P],
-    "mg_unpack": [P, P, I, I, I, I, LL, P],
-    "mg_sweep": [P, P, P, P, P, P, I, I, I, I, I, LL, P],
-    "mg_residual_restrict": [P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, P],
-    "mg_zero_restrict2": [P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, I, LL, P],
-    "mg_zero_restrict2_send": [P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, I, LL, P, I, I, I, I, P],
-    "mg_zero_restrict_send": [P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, P, I, I, I, I, P],
-    "mg_sweep_restrict": [P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, P, P, P, P],
-    "mg_prolong_sweep": [P, P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, P],
-    "mg_prolong2": [P, P, P, P, P, P, P, P, P, I, P, I, "S", I, I, I, I, LL, I, LL, I, LL, P],
-    "mg_prolong_add": [P, P, P, P, P, I, "S", I, I, I, I, LL, I, LL, P],
-    "mg_residual_norm": [P, P, P, P, I, P, P, I, I, I, I, LL, I, I, I, I, P],
-    "mg_cycle_join": [P, P, P, P, P, P, P, P, P, I, P, I, P, I, "S", "S", I, I, I, I, LL, I, LL, P, P, P, P],
-    "mg_cycle_join_rects": [P, P, P, P, P, P, P, P, P, I, P, I, P, I, "S", "S", I, I, I, I, LL, I, LL, I, P, P],
-    "mg_hsweep": [P, P, P, P, P, P, P, I, P, I, I, I, I, I, LL, P],
-    "mg_hsweep_restrict": [P, P, P, P, P, P, P, P, I, P, I, P, I, "S", I, I, I, I, LL, I, LL, P],
-    "mg_prolong_hsweep": [P, P, P, P, P, P, P, P, P, I, P, I, P, I, "S", I, I, I, I, LL, I, LL, P],
-    "mg_coarse_tail": [P, P, I, I, I, I, LL, P, P, P, I, P, P, "S", "S", I, I, I, I, P],
-    "mg_coarse_tail_ext": [P, P, I, I, I, LL, I, P, P, I, P, P, "S", "S", I, P],
-    "mg_hjac_tail": [P, P, I, I, I, I, LL, P, P, P, I, P, P, P, I, "S", "S", I, I, I, P],
-    # several coarse levels per launch (pointer arrays: ptr_array())
-    "mg_mid_down": [P, P, I, I, I, I, P, P, I, P, I, "S", I, I, P],
-    "mg_mid_down_gathered": [P, P, I, I, I, I, P, P, I, P, I, "S", I, I, P, I, I, I, I, P],
-    "mg_mid_up": [P, P, P, P, I, I, I, I, P, P, I, P, I, "S", I, I, P],
-    "mg_hmid_down": [P, P, P, I, I, I, P, P, I, P, I, P, I, "S", I, P],
-    "mg_hmid_up": [P, P, P, P, P, I, I, I, P, P, I, P, I, P, I, "S", I, P],
-    # Krylov vector operations (feanet_amd.pcg): (..., B, H, W, ld, bstride, stream)
-    "pcg_residual": [P, P, P, P, P, I, P, I, I, I, I, LL, P],
-    "pcg_direction": [P, P, P, P, P, I, P, P, I, I, I, I, LL, P],
-    "pcg_update": [P, P, P, P, P, I, P, P, I, I, I, I, LL, P],
-    "pcg_dot": [P, P, P, I, I, I, I, LL, P],
+    "knet_apply_adj": "P g, P out, P pid, P ktab, I ntab, I B, I H, I W, P stream",
+    "jacobi_sweep_adj": "P g, P gu, P gf, P pid, P ktab, P omd, I ntab, P geo, LL geo_bs, I B, I H, I W, P stream",
+    "restrict_adj": "P g, I C, P gx, P pid, P rtab, I ntab, S w0, I B, I H, I W, P stream",
+    "prolong_adj": "P g, I C, P ge, P pidc, P ptab, I ntab, S w1, I B, I Hc, I Wc, P stream",
+    "transfer_weight_grad": "P cf, I c_split, P ff, I f_split, I C, I interior, S scale, P gw, P ws, I B, I Hc, "
+                            "I Wc, P stream",
+    "stencil_weight_grad": "P g, P u, P pid, I ntab, S scale, P gw, P ws, I B, I H, I W, P stream",
+    # framed level ops
+    "mg_pack": "P src, P dst, P geo, LL geo_bstride, P bc, LL bc_bstride, I B, I H, I W, I ld, LL bstride, P stream",
+    "mg_unpack": "P src, P dst, I B, I H, I W, I ld, LL bstride, P stream",
+    "mg_sweep": "P u, P f, P out, P pid, P ktab, P omd, I ntab, I B, I H, I W, I ld, LL bstride, P stream",
+    "mg_residual_restrict": "P u, P f, P v_out, P fc, P pid, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I B, "
+                            "I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "mg_zero_restrict2": "P f, P fc, P fc2, P pid, P pidc, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I B, I H, "
+                         "I W, I ld, LL bstride, I ldc, LL bstridec, I ldc2, LL bstridec2, P stream",
+    "mg_zero_restrict2_send": "P f, P fc, P fc2, P pid, P pidc, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I B, "
+                              "I H, I W, I ld, LL bstride, I ldc, LL bstridec, I ldc2, LL bstridec2, P send, I r0, "
+                              "I r1, I c0, I c1, P stream",
+    "mg_zero_restrict_send": "P f, P fc, P pid, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I B, I H, I W, I ld, "
+                             "LL bstride, I ldc, LL bstridec, P send, I r0, I r1, I c0, I c1, P stream",
+    "mg_sweep_restrict": "P u, P f, P u_out, P fc, P pid, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I B, I H, "
+                         "I W, I ld, LL bstride, I ldc, LL bstridec, P norm_ws, P norm_hist, P norm_cnt, P stream",
+    "mg_prolong_sweep": "P u, P ec, P f, P out, P pid, P pidc, P ktab, P omd, I ntab, P ptab, I nptab, S w1, I B, "
+                        "I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "mg_prolong2": "P fc, P ec2, P f, P out, P pid, P pidc, P pidc2, P ktab, P omd, I ntab, P ptab, I nptab, S w1, "
+                   "I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, I ldc2, LL bstridec2, P stream",
+    "mg_prolong_add": "P u, P ec, P out, P pidc, P ptab, I nptab, S w1, I B, I H, I W, I ld, LL bstride, I ldc, "
+                      "LL bstridec, P stream",
+    "mg_residual_norm": "P u, P f, P pid, P ktab, I ntab, P out, P ws, I B, I H, I W, I ld, LL bstride, I rlo, "
+                        "I rhi, I clo, I chi, P stream",
+    "mg_cycle_join": "P u, P ec, P f, P u_out, P fc, P pid, P pidc, P ktab, P omd, I ntab, P ptab, I nptab, P rtab, "
+                     "I nrtab, S w1, S w0, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, P norm_ws, "
+                     "P norm_hist, P norm_cnt, P stream",
+    "mg_cycle_join_rects": "P u, P ec, P f, P u_out, P fc, P pid, P pidc, P ktab, P omd, I ntab, P ptab, I nptab, "
+                           "P rtab, I nrtab, S w1, S w0, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, "
+                           "I nrect, P rects, P stream",
+    "mg_hsweep": "P u, P u_raw, P f, P out, P pid, P ktab, P omd, I ntab, P hw, I nlayers, I B, I H, I W, I ld, "
+                 "LL bstride, P stream",
+    "mg_hsweep_restrict": "P u, P u_raw, P f, P out, P fc, P pid, P ktab, P omd, I ntab, P hw, I nlayers, P rtab, "
+                          "I nrtab, S w0, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "mg_prolong_hsweep": "P u, P u_raw, P ec, P f, P out, P pid, P pidc, P ktab, P omd, I ntab, P hw, I nlayers, "
+                         "P ptab, I nptab, S w1, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "mg_coarse_tail": "P f_t, P v_t, I Ht, I Wt, I nlev, I ld_t, LL bs_t, P pid_levels, P ktab, P omd, I ntab, "
+                      "P rtab, P ptab, S w0, S w1, I nu1, I nu2, I q2, I B, P stream",
+    "mg_coarse_tail_ext": "P f_x, P v_x, I Hx, I Wx, I ld_x, LL bs_x, I nlev, P ktab, P omd, I ntab, P rtab, "
+                          "P ptab, S w0, S w1, I B, P stream",
+    "mg_hjac_tail": "P f_t, P u_t, I Ht, I Wt, I nlev, I ld_t, LL bs_t, P pid_levels, P ktab, P omd, I ntab, "
+                    "P rtab, P ptab, P hw, I nlayers, S w0, S w1, I nu1, I nu2, I B, P stream",
+    # several coarse levels per launch (pointer arrays: PtrArray)
+    "mg_mid_down": "P f, P pid, I k, I B, I H, I W, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I TR, I TC, P stream",
+    "mg_mid_down_gathered": "P f, P pid, I k, I B, I H, I W, P ktab, P omd, I ntab, P rtab, I nrtab, S w0, I TR, "
+                            "I TC, P gsrc, I Pr, I Pc, I gcr, I gcc, P stream",
+    "mg_mid_up": "P f, P e, P out, P pid, I k, I B, I H, I W, P ktab, P omd, I ntab, P ptab, I nptab, S w1, I TR, "
+                 "I TC, P stream",
+    "mg_hmid_down": "P f, P u, P pid, I B, I H, I W, P ktab, P omd, I ntab, P hw, I nlayers, P rtab, I nrtab, S w0, "
+                    "I T, P stream",
+    "mg_hmid_up": "P f, P u, P e, P out, P pid, I B, I H, I W, P ktab, P omd, I ntab, P hw, I nlayers, P ptab, "
+                  "I nptab, S w1, I T, P stream",
+    # Krylov vector operations (feanet_amd.pcg)
+    "pcg_residual": "P x, P f, P r, P pid, P ktab, I ntab, P part, I B, I H, I W, I ld, LL bstride, P stream",
+    "pcg_direction": "P z, P p_in, P p_out, P pid, P ktab, I ntab, P scalars, P part, I B, I H, I W, I ld, "
+                     "LL bstride, P stream",
+    "pcg_update": "P p, P x, P r, P pid, P ktab, I ntab, P scalars, P part, I B, I H, I W, I ld, LL bstride, P stream",
+    "pcg_dot": "P r, P z, P part, I B, I H, I W, I ld, LL bstride, P stream",
 }
 _EXTRA = {
-    "fea_abi_version": ([], I),
-    "fea_mg_layout": ([I, I, I, ctypes.POINTER(I), ctypes.POINTER(LL)], I),
-    "fea_norm_workspace_bytes": ([I, I, I], ctypes.c_size_t),
-    "fea_mg_join_norm_parts": ([I, I, I, I], LL),
-    "fea_norm_append": ([P, LL, LL, I, I, P, P, P], I),
-    "fea_mg_coarse_tail_lds_bytes": ([I, I, I, I, I], ctypes.c_size_t),
-    "fea_mg_hjac_tail_lds_bytes": ([I, I, I, I, I], ctypes.c_size_t),
-    "fea_mg_mid_lds_bytes": ([I, I, I, I, I, I], LL),
-    "fea_mg_hmid_lds_bytes": ([I, I, I, I, I], LL),
-    "fea_interface_pattern_map": ([P, LL, I, I, F64, P], I),
-    "fea_dd_copy_blocks": ([P, I, I, I, P], I),
-    "fea_dd_copy_rects": ([P, I, I, P], I),
-    "fea_pcg_parts": ([I, I, I], LL),
-    "fea_pcg_scalar_step": ([P, LL, P, P, I, I, I, P], I),
-    # fp64 Krylov fields with an fp32 preconditioner: (..., B, H, W, ld, bstride, ld32, bstride32, stream)
-    "fea_pcg_narrow_f64f32": ([P, P, P, P, I, I, I, I, LL, I, LL, P], I),
-    "fea_pcg_dot_f64f32": ([P, P, P, I, I, I, I, LL, I, LL, P], I),
-    "fea_pcg_direction_f64f32": ([P, P, P, P, P, I, P, P, I, I, I, I, LL, I, LL, P], I),
-    "fea_pcg_update_f64f32": ([P, P, P, P, P, P, I, P, P, P, I, I, I, I, LL, I, LL, P], I),
-    "fea_stencil_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),
-    "fea_stencil_weight_grad_ws_bytes_f64": ([I, I, I, I], ctypes.c_size_t),
-    "fea_transfer_weight_grad_ws_bytes_f32": ([I, I, I, I], ctypes.c_size_t),
-    "fea_transfer_weight_grad_ws_bytes_f64": ([I, I, I, I], ctypes.c_size_t),
+    "fea_abi_version": ("", I),
+    "fea_mg_layout": ("I H, I W, I elem_size, PI ld, PLL bstride", I),
+    "fea_norm_workspace_bytes": ("I B, I H, I W", ctypes.c_size_t),
+    "fea_mg_join_norm_parts": ("I B, I H, I W, I elem_size", LL),
+    "fea_norm_append": ("P ws, LL stride, LL per, I B, I nrows, P hist, P cnt, P stream", I),
+    "fea_mg_coarse_tail_lds_bytes": ("I Ht, I Wt, I nlev, I elem_size, I multi", ctypes.c_size_t),
+    "fea_mg_hjac_tail_lds_bytes": ("I Ht, I Wt, I nlev, I elem_size, I multi", ctypes.c_size_t),
+    "fea_mg_mid_lds_bytes": ("I up, I k, I TR, I TC, I elem_size, I multi", LL),
+    "fea_mg_hmid_lds_bytes": ("I up, I T, I nlayers, I elem_size, I multi", LL),
+    "fea_interface_pattern_map": ("P out, LL ld, I N, I shape, D size, P stream", I),
+    "fea_dd_copy_blocks": ("P blocks, I nblocks, I elem_size, I to_stage, P stream", I),
+    "fea_dd_copy_rects": ("P rects, I nrects, I elem_size, P stream", I),
+    "fea_pcg_parts": ("I H, I W, I elem_size", LL),
+    "fea_pcg_scalar_step": ("P part, LL per, P scalars, P hist, I hist_rows, I B, I step, P stream", I),
+    # fp64 Krylov fields with an fp32 preconditioner
+    "fea_pcg_narrow_f64f32": ("P r, P r32, P scalars, P sb, I B, I H, I W, I ld, LL bstride, I ld32, LL bstride32, "
+                              "P stream", I),
+    "fea_pcg_dot_f64f32": ("P r, P z32, P part, I B, I H, I W, I ld, LL bstride, I ld32, LL bstride32, P stream", I),
+    "fea_pcg_direction_f64f32": ("P z32, P p_in, P p_out, P pid, P ktab, I ntab, P scalars, P part, I B, I H, I W, "
+                                 "I ld, LL bstride, I ld32, LL bstride32, P stream", I),
+    "fea_pcg_update_f64f32": ("P p, P x, P r, P r32, P pid, P ktab, I ntab, P scalars, P sb, P part, I B, I H, I W, "
+                              "I ld, LL bstride, I ld32, LL bstride32, P stream", I),
+    "fea_stencil_weight_grad_ws_bytes_f32": ("I ntab, I B, I H, I W", ctypes.c_size_t),
+    "fea_stencil_weight_grad_ws_bytes_f64": ("I ntab, I B, I H, I W", ctypes.c_size_t),
+    "fea_transfer_weight_grad_ws_bytes_f32": ("I C, I B, I Hc, I Wc", ctypes.c_size_t),
+    "fea_transfer_weight_grad_ws_bytes_f64": ("I C, I B, I Hc, I Wc", ctypes.c_size_t),
 }
+# as lists of "TYPE param" fields: len() of an entry is its number of C arguments
+_SIGS = {name: sig.split(", ") for name, sig in _SIGS.items()}
+_EXTRA = {name: (sig.split(", ") if sig else [], res) for name, (sig, res) in _EXTRA.items()}
 
 _lib = None
+
+
+def _argtypes(sig, S=None):
+    return [S if t == "S" else _CTYPES[t] for t in (p.split()[0] for p in sig)]
+
+
+_NAMES = {}  # launch name -> parameter names in C-ABI order, without the trailing stream
+
+
+def _names(name):
+    """Parameter names of a launch record's entry point: a typed pair's base name, or a dtype-free fea_<name>."""
+    if name not in _NAMES:
+        sig = _SIGS.get(name) or _EXTRA.get("fea_" + name, ([],))[0]
+        names = [p.split()[1] for p in sig]
+        if names[-1:] != ["stream"]:
+            raise TypeError(f"feanet_amd: no entry point fea_{name} that launches on a stream")
+        _NAMES[name] = tuple(names[:-1])
+    return _NAMES[name]
+
+
+def launch(name, **kw):
+    """A launch record (name, args): args the positional tuple of fea_<name>'s parameters in header order, without
+    the stream, every one given by name (a NULL pointer is written u=None)."""
+    names = _names(name)
+    for n in names:
+        if n not in kw:
+            raise TypeError(f"feanet_amd: fea_{name} launch lacks parameter {n!r}")
+    if len(kw) != len(names):
+        raise TypeError(f"feanet_amd: fea_{name} has no parameter {sorted(set(kw) - set(names))[0]!r}")
+    return (name, tuple(kw[n] for n in names))
+
+
+def arg(launch, pname):
+    """Value of parameter `pname` in a launch record."""
+    name, args = launch
+    names = _names(name)
+    if pname not in names:
+        raise TypeError(f"feanet_amd: fea_{name} has no parameter {pname!r}")
+    return args[names.index(pname)]
+
+
+def replace(launch, **kw):
+    """The launch record with the given parameters changed."""
+    name, args = launch
+    names = _names(name)
+    args = list(args)
+    for n, v in kw.items():
+        if n not in names:
+            raise TypeError(f"feanet_amd: fea_{name} has no parameter {n!r}")
+        args[names.index(n)] = v
+    return (name, tuple(args))
 
 
 def exported_symbols():
@@ -123,16 +210,16 @@ def lib():
         if lab and not hasattr(L, name):
             return None
         return getattr(L, name)
-    for name, (args, res) in _EXTRA.items():
+    for name, (sig, res) in _EXTRA.items():
         fn = sym(name)
         if fn is not None:
-            fn.argtypes = args
+            fn.argtypes = _argtypes(sig)
             fn.restype = res
-    for base, args in _SIGS.items():
+    for base, sig in _SIGS.items():
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")
             if fn is not None:
-                fn.argtypes = [S if a == "S" else a for a in args]
+                fn.argtypes = _argtypes(sig, S)
                 fn.restype = I
     if L.fea_abi_version() != ABI_VERSION:
         raise RuntimeError("feanet_amd: libfeanet_hip.so ABI version mismatch; rebuild it")

@@ -40,7 +40,7 @@ import torch
 
 from . import _lib, mesh_setup as ms, ops
 from .schedule import hjac_schedule, pair_prolongations, pair_restrictions, vcycle_schedule
-from .solver import MultigridSolver
+from .solver import MultigridSolver, first_sweep_raw
 
 
 def global_levels(m, n):
@@ -374,6 +374,11 @@ def _launch_list(launches, dtype, stream):
             _lib.call(name, dtype, *args, stream.cuda_stream)
 
 
+def _params(launch):
+    """A C-ABI launch record's arguments by parameter name (for the entry points that extend another's list)."""
+    return dict(zip(_lib._names(launch[0]), launch[1]))
+
+
 _DD_RECT_WORDS = 6  # fea_dd_copy_rects record: int64 dst, src, dst_ld, src_ld, rows, cols
 
 
@@ -545,6 +550,8 @@ class DDSolver:
         self._state = "a"
         self._raw = None  # smoother="hjac": the un-reset initial iterate the first cycle after load() reads
         self._hjac_first = False
+        self._gstage = self._gsend = None  # 2-D blocks: the all-gather's receive and send buffers (gather_target)
+        self._rects = None  # join_rects(), cached
         self.norm_sq = torch.zeros(batch, dtype=torch.float64, device=self.device)
 
     # ------------------------------------------------------------------ data
@@ -718,26 +725,28 @@ class DDSolver:
         """The _send form of the zero-guess restriction `launch` when it computes f_Ld (2-D blocks: it then also
         stores this rank's block of f_Ld into the all-gather's send buffer, fea_mg_zero_restrict2_send /
         fea_mg_zero_restrict_send), else None."""
-        name, args = launch
+        name, arg = launch[0], _lib.arg
         f_ld = self.local.levels[self.Ld].f.data_ptr()
         pl, ql = self.parts[self.Ld], self.cparts[self.Ld]
-        blk = (self._gsend.data_ptr(), pl.lo, pl.lo + self.part.rows_per_rank(self.Ld), ql.lo,
-               ql.lo + self.part.cols_per_rank(self.Ld))
-        if name == "mg_zero_restrict2" and args[2] == f_ld:
-            return ("mg_zero_restrict2_send", tuple(args) + blk)
-        if name == "mg_residual_restrict" and args[3] == f_ld and args[0] is None and args[2] is None:
-            # (u, f, v_out, fc, pid, ktab, omd, ntab, rtab, nrtab, w0, geometry ...) -> (f, fc, pid, ..., geometry ...)
-            return ("mg_zero_restrict_send", (args[1], args[3]) + tuple(args[4:]) + blk)
+        blk = dict(send=self._gsend.data_ptr(), r0=pl.lo, r1=pl.lo + self.part.rows_per_rank(self.Ld), c0=ql.lo,
+                   c1=ql.lo + self.part.cols_per_rank(self.Ld))
+        if name == "mg_zero_restrict2" and arg(launch, "fc2") == f_ld:
+            return _lib.launch("mg_zero_restrict2_send", **_params(launch), **blk)
+        if (name == "mg_residual_restrict" and arg(launch, "fc") == f_ld and arg(launch, "u") is None
+                and arg(launch, "v_out") is None):
+            carried = ("f", "fc", "pid", "ktab", "omd", "ntab", "rtab", "nrtab", "w0", "B", "H", "W", "ld", "bstride",
+                       "ldc", "bstridec")  # all but u and v_out (both NULL: the zero-guess form)
+            return _lib.launch("mg_zero_restrict_send", **{p: arg(launch, p) for p in carried}, **blk)
         return None
 
     def _gathered_form(self, launch):
         """The coarse plan's first launch in its _gathered form when it is the mid_down over the coarse top level (it
         then reads f_Ld's blocks from the all-gather's buffer and places them, fea_mg_mid_down_gathered), else None."""
-        name, args = launch
-        if name != "mg_mid_down" or args[0].arr[0] != self.coarse.levels[0].f.data_ptr():
+        if launch[0] != "mg_mid_down" or _lib.arg(launch, "f").arr[0] != self.coarse.levels[0].f.data_ptr():
             return None
         c, cc = self.part.rows_per_rank(self.Ld), self.part.cols_per_rank(self.Ld)
-        return ("mg_mid_down_gathered", tuple(args) + (self._gstage.data_ptr(), self.Pr, self.Pc, c, cc))
+        return _lib.launch("mg_mid_down_gathered", **_params(launch), gsrc=self._gstage.data_ptr(), Pr=self.Pr,
+                           Pc=self.Pc, gcr=c, gcc=cc)
 
     def _scatter_direct(self, st, nxt):
         """Can the scatter step `st` (coarse solution -> level Ld's buffer st[1]) be dropped, the next step reading
@@ -752,19 +761,15 @@ class DDSolver:
         return self.local.levels[self.Ld].pid is None and self.coarse.levels[0].pid is None
 
     def _read_coarse_in_place(self, launch):
-        """mg_prolong2's launch with its level-(l+2) correction (argument 1; row pitch and sample stride: the last
-        two arguments) taken from the coarse solver's solution window of this rank instead of level Ld."""
-        name, args = launch
-        assert name == "mg_prolong2", name
+        """mg_prolong2's launch with its level-(l+2) correction (ec2; row pitch and sample stride: ldc2, bstridec2)
+        taken from the coarse solver's solution window of this rank instead of level Ld."""
+        assert launch[0] == "mg_prolong2", launch[0]
         Lc = self.coarse.levels[0]
         pl = self.parts[self.Ld]
         gc0 = self.cparts[self.Ld].gr0 if self.Pc > 1 else 0
         buf = Lc.buf(self.coarse_end)
         win = buf.data_ptr() + (pl.gr0 * Lc.ld + gc0) * buf.element_size()
-        args = list(args)
-        args[1] = win
-        args[-2], args[-1] = Lc.ld, Lc.bs
-        return (name, tuple(args))
+        return _lib.replace(launch, ec2=win, ldc2=Lc.ld, bstridec2=Lc.bs)
 
     def joinable(self):
         return self.local._joinable()
@@ -789,19 +794,15 @@ class DDSolver:
         return res
 
     def _first_sweep_raw(self, segs):
-        """The segments with the cycle's first level-0 HRelax sweep given the un-reset iterate (its u_raw slot,
-        argument 1), as MultigridSolver._vcycles_plain does for the first cycle after load()."""
+        """The segments with the cycle's first level-0 HRelax sweep given the un-reset iterate, as
+        MultigridSolver._vcycles_plain does for the first cycle after load() (solver.first_sweep_raw)."""
         f0 = self.local.levels[0].f.data_ptr()
         out, done = [], False
         for kind, launches, lvl0 in segs:
             if kind == "k" and not done:
-                launches = list(launches)
-                for i, (name, args) in enumerate(launches):
-                    fi = {"mg_hsweep": 2, "mg_hsweep_restrict": 2, "mg_prolong_hsweep": 3}.get(name)
-                    if fi is not None and args[fi] == f0:
-                        launches[i] = (name, (args[0], self._raw.data_ptr()) + tuple(args[2:]))
-                        done = True
-                        break
+                first = first_sweep_raw(list(launches), f0, self._raw.data_ptr())
+                if first is not None:
+                    launches, done = first, True
             out.append((kind, launches, lvl0))
         return out
 
@@ -892,7 +893,7 @@ class DDSolver:
         c = self.part.rows_per_rank(self.Ld)
         if self.Pc == 1:
             return _rows(Lc.f, Lc.B, Lc.bs, Lc.ld, 1, 1 + self.P * c)
-        if getattr(self, "_gstage", None) is None:
+        if self._gstage is None:
             cc = self.part.cols_per_rank(self.Ld)
             # zero-filled once: a communicator that moves nothing (the projection's PackComm) then leaves a
             # deterministic coarse right-hand side instead of whatever the allocator handed back
@@ -906,9 +907,8 @@ class DDSolver:
         Lc = self.coarse.levels[0]
         c, cc = self.part.rows_per_rank(self.Ld), self.part.cols_per_rank(self.Ld)
         Pr, Pc, B = self.Pr, self.Pc, Lc.B
-        off = 128 // Lc.f.element_size() - 1
         dst = Lc.f.as_strided((B, Pr, c, Pc, cc), (Lc.bs, c * Lc.ld, Lc.ld, cc, 1),
-                              Lc.f.storage_offset() + 2 * Lc.ld + off + 1)
+                              Lc.f.storage_offset() + 2 * Lc.ld + Lc.off + 1)
         return dst, blocks.view(Pr, Pc, B, c, cc).permute(2, 0, 3, 1, 4)
 
     def gather_place(self, blocks):
@@ -1102,7 +1102,7 @@ class DDSolver:
         them ({I0, I1, c0, c1}: coarse rows, odd fine-column bounds): the border holds every node the cycle's halo
         exchange sends (owned nodes within D0 fine / D1 coarse lines of an edge with a neighbour) or receives (the
         ghost lines), so the interior join can run while the messages are in flight."""
-        if getattr(self, "_rects", None) is not None:
+        if self._rects is not None:
             return self._rects
         D0, D1 = self.depths
         p0, q0, p1, q1 = self.parts[0], self.cparts[0], self.parts[1], self.cparts[1]
@@ -1138,14 +1138,16 @@ class DDSolver:
         if inner is None or not border:
             return False
         j = nj[0]
-        jargs = launches[j][1][:23]  # mg_cycle_join's arguments up to bsc (no norm)
+        join = _params(launches[j])
+        for p in ("norm_ws", "norm_hist", "norm_cnt"):  # the rectangles' join takes no norm
+            del join[p]
         rects = self.__dict__.setdefault("_rect_arrays", {})
-        arrs = []
+        joins = []
         for key, rs in (("border", border), ("inner", [inner])):
             if key not in rects:
                 import ctypes
                 rects[key] = (ctypes.c_int * (4 * len(rs)))(*[x for r in rs for x in r])
-            arrs.append((len(rs), ctypes_addr(rects[key])))
+            joins.append(_lib.launch("mg_cycle_join_rects", **join, nrect=len(rs), rects=ctypes_addr(rects[key])))
         main = torch.cuda.current_stream(self.device)
         side = self.__dict__.get("_side")
         if side is None:
@@ -1154,11 +1156,11 @@ class DDSolver:
         side.wait_stream(main)
         st = segs[i + 1][1]
         with torch.cuda.stream(side):
-            _launch_list([("mg_cycle_join_rects", jargs + arrs[0])] + launches[j + 1:], self.dtype, side)
+            _launch_list([joins[0]] + launches[j + 1:], self.dtype, side)
             now, later = _split_exchanges(st[1], self.overlap_l0)
             items = list(now) + list(later)
             self.comm.exchange_many(self, items, packed=len(st) > 2 and st[2])
-        _launch_list([("mg_cycle_join_rects", jargs + arrs[1])], self.dtype, main)
+        _launch_list([joins[1]], self.dtype, main)
         main.wait_stream(side)
         return True
 

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib, mesh_setup as ms, ops
-from .solver import MultigridSolver, _Level
+from .solver import MultigridSolver, _Level, run_segment
 
 # scalar block layout and steps: include/feanet_hip.h (FEA_PCG_*)
 NSCALARS = 12
@@ -96,6 +96,7 @@ class PCGSolver:
         self.use_graph = bool(graph)
         self.check_every = int(check_every)
         self._pf = mg.levels[0].f  # the preconditioner's right-hand side buffer
+        self._bc = None  # mixed precision: the Dirichlet values in fp64 (else the preconditioner holds them)
         if self.mixed:
             # the Krylov fields' own fp64 frame: its three fields are r, x and b, and its pattern map and stencil
             # table are kapply<double>'s (pattern windows hold byte offsets of sizeof(T) table rows)
@@ -105,7 +106,6 @@ class PCGSolver:
             self.r, self.x, self.b = L0.f, L0.a, L0.b
             p0, p1 = (torch.zeros_like(L0.a) for _ in range(2))
             self.sb = torch.ones(self.B, dtype=torch.float64, device=self.device)  # per-sample scale s_b
-            self._bc = None
         else:
             self.L0 = L0 = mg.levels[0]
             self.ktab = mg.ktab
@@ -114,7 +114,7 @@ class PCGSolver:
         self.p = (p0, p1)
         self._parity = 0  # the next iteration reads p[_parity] and writes p[1 - _parity]
         self._zname = None
-        self.per = int(_lib.lib().fea_pcg_parts(L0.H, L0.W, 4 if dtype == torch.float32 else 8))
+        self.per = int(_lib.lib().fea_pcg_parts(L0.H, L0.W, L0.esz))
         self.part = torch.zeros(self.B * self.per, dtype=torch.float64, device=self.device)
         self.sc = torch.zeros((self.B, NSCALARS), dtype=torch.float64, device=self.device)
         self.hist = torch.zeros((self.HIST_ROWS, self.B), dtype=torch.float64, device=self.device)
@@ -176,14 +176,25 @@ class PCGSolver:
         L0 = self.L0
         return (None if L0.pid is None else L0.pid.data_ptr(), self.ktab.data_ptr(), self.mg.ntab)
 
+    def _stencil(self):
+        pid, ktab, ntab = self._kargs()
+        return dict(pid=pid, ktab=ktab, ntab=ntab)
+
+    def _geom(self):
+        """The Krylov fields' frame by parameter name; mixed precision: with the preconditioner's fp32 level-0 frame."""
+        g = self.L0.geom_kw()
+        if self.mixed:
+            g["ld32"], g["bstride32"] = self._g32()
+        return g
+
     def _g32(self):
         """(ld, bstride) of the preconditioner's fp32 level-0 frame (mixed precision)."""
         P0 = self.mg.levels[0]
         return (P0.ld, P0.bs)
 
     def _scalar(self, step):
-        return ("pcg_scalar_step", (self.part.data_ptr(), self.per, self.sc.data_ptr(), self.hist.data_ptr(),
-                                    self.hist.shape[0], self.B, step))
+        return _lib.launch("pcg_scalar_step", part=self.part.data_ptr(), per=self.per, scalars=self.sc.data_ptr(),
+                           hist=self.hist.data_ptr(), hist_rows=self.hist.shape[0], B=self.B, step=step)
 
     def _launch(self, launches):
         stream = self._stream()
@@ -199,65 +210,58 @@ class PCGSolver:
         mg, L0 = self.mg, self.L0
         if u0 is not None:
             u0 = self._check_field(u0, "u0")
-        self._pack(u0, self.x, bc=self._bc if self.mixed else getattr(mg, "_bc", None))
+        self._pack(u0, self.x, bc=self._bc if self.mixed else mg._bc)
         self.p[0].zero_()
         self.p[1].zero_()
         self.sc.zero_()
         self.sc[:, EPS] = float(eps)
         self.sc[:, RTOL] = -1.0 if rtol is None else float(rtol)
         self._parity = 0
-        self._launch([("pcg_residual", (self.x.data_ptr(), self.b.data_ptr(), self.r.data_ptr()) + self._kargs() +
-                       (self.part.data_ptr(),) + L0.geom()), self._scalar(STEP_INIT)])
+        self._launch([_lib.launch("pcg_residual", x=self.x.data_ptr(), f=self.b.data_ptr(), r=self.r.data_ptr(),
+                                  part=self.part.data_ptr(), **self._stencil(), **L0.geom_kw()),
+                      self._scalar(STEP_INIT)])
         if self.mixed:  # fixes s_b from ||r0|| and hands the preconditioner float(r0 s_b)
-            self._launch([("pcg_narrow_f64f32", (self.r.data_ptr(), self._pf.data_ptr(), self.sc.data_ptr(),
-                                                 self.sb.data_ptr()) + L0.geom() + self._g32())])
+            self._launch([_lib.launch("pcg_narrow_f64f32", r=self.r.data_ptr(), r32=self._pf.data_ptr(),
+                                      scalars=self.sc.data_ptr(), sb=self.sb.data_ptr(), **self._geom())])
         self._loaded = True
 
     # ------------------------------------------------------------------ iteration
     def _iteration(self, q):
         """Launches of one iteration reading p[q], writing p[1 - q]."""
-        mg, L0, P0 = self.mg, self.L0, self.mg.levels[0]
+        mg, P0 = self.mg, self.mg.levels[0]
         plan, end = mg._plan("a")  # from a zero guess: the plan does not depend on the start buffer
         if self._zname is None:
             self._zname = end
         assert end == self._zname and P0.buf(end).data_ptr() != self._pf.data_ptr(), "the preconditioner's output moved"
         z = P0.buf(end).data_ptr()
-        g, ka, part, sc = L0.geom(), self._kargs(), self.part.data_ptr(), self.sc.data_ptr()
+        launch, g, st = _lib.launch, self._geom(), self._stencil()
+        part, sc, r, x = self.part.data_ptr(), self.sc.data_ptr(), self.r.data_ptr(), self.x.data_ptr()
         pin, pout = self.p[q].data_ptr(), self.p[1 - q].data_ptr()
         if self.mixed:
-            g = g + self._g32()
             return list(plan) + [
-                ("pcg_dot_f64f32", (self.r.data_ptr(), z, part) + g), self._scalar(STEP_RZ),
-                ("pcg_direction_f64f32", (z, pin, pout) + ka + (sc, part) + g), self._scalar(STEP_PAP),
-                ("pcg_update_f64f32", (pout, self.x.data_ptr(), self.r.data_ptr(), self._pf.data_ptr()) + ka +
-                 (sc, self.sb.data_ptr(), part) + g), self._scalar(STEP_RR)]
+                launch("pcg_dot_f64f32", r=r, z32=z, part=part, **g), self._scalar(STEP_RZ),
+                launch("pcg_direction_f64f32", z32=z, p_in=pin, p_out=pout, scalars=sc, part=part, **st, **g),
+                self._scalar(STEP_PAP),
+                launch("pcg_update_f64f32", p=pout, x=x, r=r, r32=self._pf.data_ptr(), scalars=sc,
+                       sb=self.sb.data_ptr(), part=part, **st, **g),
+                self._scalar(STEP_RR)]
         return list(plan) + [
-            ("pcg_dot", (self.r.data_ptr(), z, part) + g), self._scalar(STEP_RZ),
-            ("pcg_direction", (z, pin, pout) + ka + (sc, part) + g), self._scalar(STEP_PAP),
-            ("pcg_update", (pout, self.x.data_ptr(), self.r.data_ptr()) + ka + (sc, part) + g),
-            self._scalar(STEP_RR)]
+            launch("pcg_dot", r=r, z=z, part=part, **g), self._scalar(STEP_RZ),
+            launch("pcg_direction", z=z, p_in=pin, p_out=pout, scalars=sc, part=part, **st, **g),
+            self._scalar(STEP_PAP),
+            launch("pcg_update", p=pout, x=x, r=r, scalars=sc, part=part, **st, **g), self._scalar(STEP_RR)]
 
     def krylov_launches_per_iteration(self):
         return 6
 
     def _run_block(self, q, nb):
+        """nb iterations from parity q: eager, then captured, then replayed (solver.run_segment)."""
         key = (q, nb, self.hist.data_ptr())
-        if not self.use_graph or self._eager_runs.get(key, 0) == 0:
-            self._eager_runs[key] = 1
-            for i in range(nb):
-                self._launch(self._iteration((q + i) % 2))
-            return
         g = self._graphs.get(key)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.graph(g, stream=s):
-                for i in range(nb):
-                    self._launch(self._iteration((q + i) % 2))
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            self._graphs[key] = g
-        g.replay()
+        if g is not None:  # captured: replay without rebuilding the launch list
+            g.replay()
+            return
+        run_segment(self, key, [rec for i in range(nb) for rec in self._iteration((q + i) % 2)])
 
     def iterate(self, k=1):
         """k iterations on the resident state (asynchronous; no host sync)."""

@@ -33,6 +33,40 @@ _SOLVERS = weakref.WeakValueDictionary()  # handle -> live MultigridSolver (torc
 _HANDLES = itertools.count(1)
 
 
+def run_segment(s, key, launches):
+    """Run the launch list `launches` of solver s (its _launch, use_graph, _eager_runs, _graphs) under `key`: eager
+    the first time (lazy buffers and pointer arrays exist afterwards), captured as a HIP graph the second, replayed
+    after."""
+    if not s.use_graph or s._eager_runs.get(key, 0) == 0:
+        s._eager_runs[key] = s._eager_runs.get(key, 0) + 1
+        s._launch(launches)
+        return
+    g = s._graphs.get(key)
+    if g is None:
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(s.device)
+        side.wait_stream(torch.cuda.current_stream(s.device))
+        with torch.cuda.graph(g, stream=side):
+            s._launch(launches)
+        torch.cuda.current_stream(s.device).wait_stream(side)
+        s._graphs[key] = g
+    g.replay()
+
+
+def first_sweep_raw(launches, f0, raw):
+    """`launches` with the cycle's first finest-level HRelax launch (the first whose f is level 0's, `f0`, and that
+    has a u_raw parameter) reading the un-reset iterate `raw`: the first cycle after load() (M-FEANet-mg_test.ipynb
+    :151-153).  None if there is no such launch."""
+    for i, rec in enumerate(launches):
+        try:
+            _lib.arg(rec, "u_raw")
+        except TypeError:  # not an HRelax launch (or a device copy of the decomposed solver's lists)
+            continue
+        if _lib.arg(rec, "f") == f0:
+            return launches[:i] + [_lib.replace(rec, u_raw=raw)] + launches[i + 1:]
+    return None
+
+
 def solver_by_handle(h):
     s = _SOLVERS.get(int(h))
     if s is None:
@@ -47,8 +81,9 @@ class _Level:
         self.m, self.n = m, n
         self.H, self.W = m + 1, n + 1
         self.N = self.W
-        esz = 4 if dtype == torch.float32 else 8
-        self.ld, self.bs = _lib.mg_layout(self.H, self.W, esz)
+        self.esz = 4 if dtype == torch.float32 else 8
+        self.off = 128 // self.esz - 1  # column of node 0 in a framed row: column 1 starts a 128-byte line
+        self.ld, self.bs = _lib.mg_layout(self.H, self.W, self.esz)
         self.B = B
         self.dtype = dtype
         self.device = device
@@ -60,16 +95,14 @@ class _Level:
         self.c = None  # third iterate buffer of the finest level (solve(): the block's start state)
         self.pid = None
         if pid_np is not None:
-            off = 128 // esz - 1
             p = np.zeros((self.H + 2, self.ld), np.uint8)
-            p[1:self.H + 1, off:off + self.W] = pid_np
+            p[1:self.H + 1, self.off:self.off + self.W] = pid_np
             self.pid = torch.from_numpy(p.reshape(-1)).to(device)
             self.pid = torch.cat([self.pid, torch.zeros(256, dtype=torch.uint8, device=device)])
         elif pid_shape is not None:  # (shape, size): built on the device straight into the frame
-            off = 128 // esz - 1
             self.pid = torch.zeros((self.H + 2) * self.ld + 256, dtype=torch.uint8, device=device)
             ms.interface_pattern_map_device(self.N, pid_shape[0], pid_shape[1], device=device,
-                                            out=self.pid.data_ptr() + self.ld + off, ld=self.ld)
+                                            out=self.pid.data_ptr() + self.ld + self.off, ld=self.ld)
 
     def buf(self, name):
         if name in ("zero", "c") and getattr(self, name) is None:
@@ -81,8 +114,16 @@ class _Level:
         off = 128 // t.element_size() - 1
         return t[:self.B * self.bs].view(self.B, self.H + 2, self.ld)[:, 1:self.H + 1, off:off + self.W]
 
+    def pid_view(self):
+        """[H, W] view of the framed pattern map (one byte per node, the fields' row pitch and column offset)."""
+        return self.pid[:(self.H + 2) * self.ld].view(self.H + 2, self.ld)[1:self.H + 1, self.off:self.off + self.W]
+
     def geom(self):
         return (self.B, self.H, self.W, self.ld, self.bs)
+
+    def geom_kw(self):
+        """geom() by parameter name, for _lib.launch."""
+        return dict(B=self.B, H=self.H, W=self.W, ld=self.ld, bstride=self.bs)
 
 
 class MultigridSolver:
@@ -252,14 +293,12 @@ class MultigridSolver:
             self.fine_pid = ms.interface_pattern_map_device(n + 1, shape, size, device=dev) if multi else None
         if multi:  # the framed kernels read each node's stiffness row from its own pattern (K symmetric; checked)
             for Lv in self.levels:
-                off = 128 // (4 if dtype == torch.float32 else 8) - 1
-                pv = Lv.pid[:(Lv.H + 2) * Lv.ld].view(Lv.H + 2, Lv.ld)[1:Lv.H + 1, off:off + Lv.W]
-                if ms.stencil_mirror_mismatches(ktab, pv):
+                if ms.stencil_mirror_mismatches(ktab, Lv.pid_view()):
                     raise ValueError("MultigridSolver: the stiffness table is not symmetric on this pattern map "
                                      "(the framed two-material kernels need K_ij == K_ji bit for bit)")
         self.tail_from = None
+        esz = self.levels[0].esz
         if coarse_tail:
-            esz = 4 if dtype == torch.float32 else 8
             for l in range(1, self.L):
                 Lv = self.levels[l]
                 if (Lv.H <= self.TAIL_MAX_N and Lv.W <= self.TAIL_MAX_N
@@ -269,7 +308,6 @@ class MultigridSolver:
         # learned smoother: the levels of <= 65^2 nodes whose f, u and two scratch fields fit in LDS
         self.hjac_tail_from = None
         if hjac_tail:
-            esz = 4 if dtype == torch.float32 else 8
             for l in range(1, self.L):
                 Lv = self.levels[l]
                 if (Lv.H <= 65 and Lv.W <= 65
@@ -286,6 +324,9 @@ class MultigridSolver:
         self.ws = torch.zeros(max(1, _lib.norm_workspace_bytes(self.B, m + 1, n + 1) // 8), dtype=torch.float64,
                               device=dev)
         self.norm_out = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        self._bc = None  # Dirichlet data of set_boundary ([B, 1, H, W]; None: zero)
+        self._raw = None  # smoother="hjac": the un-reset iterate load() got, read by the next cycle's first sweep
+        self._hjac_first = False
         self._state = "a"
         # joinable solvers rest BETWEEN cycles in a pipelined ("mid-cycle") state after vcycle(k): see
         # _vcycles_pipelined; None = the iterate is materialised in buffer self._state
@@ -293,6 +334,9 @@ class MultigridSolver:
         self._hist = None  # solve(): fused residual-norm history + counters (_ensure_hist)
         self._cnt = None
         self._hist_gen = 0
+        self._hist_host = None  # pinned host copy of the history (_read_hist)
+        self._trace = False  # solve(): synchronise and time every phase into _solve_log (diagnostics)
+        self._solve_log = []
         self._f1_snap = None
         self._sws = None  # solve(): per-cycle partial norm sets of a graph block
         self._bc_version = object()  # identity changes with every set_boundary (third-buffer packing)
@@ -372,7 +416,7 @@ class MultigridSolver:
     def load(self, u0=None):
         """Set the fine-grid iterate (reset_boundary applied: u*geo + bc, jacobi.py:27-29)."""
         L0 = self.levels[0]
-        bc = getattr(self, "_bc", None)
+        bc = self._bc
         if u0 is not None:
             u0 = self._check_field(u0, "u0")
         self._pack(u0, L0.a, bc=bc)
@@ -476,7 +520,7 @@ class MultigridSolver:
         level a), or None: the largest power of two whose LDS footprint fits, that gives the chip
         >= MID_MIN_TILES workgroups (or the most it can) and, going down, stages <= MID_MAX_REDUNDANCY
         times the top level's nodes."""
-        esz = 4 if self.dtype == torch.float32 else 8
+        esz = self.levels[0].esz
         multi = self.ntab > 1
         tl = self.levels[a if up else a + k]
         top = self.levels[a]
@@ -498,7 +542,7 @@ class MultigridSolver:
         """Tile size of an HJac two-level launch over levels a, a+1 (down: tile of level a+2; up: of level a):
         the largest whose LDS footprint fits and that gives >= HMID_MIN_TILES workgroups, else the smallest that
         fits (None: none does)."""
-        esz = 4 if self.dtype == torch.float32 else 8
+        esz = self.levels[0].esz
         tl = self.levels[a if up else a + 2]
         fit = [T for T in ((64, 32, 16, 8) if up else (16, 8, 4, 2))
                if _lib.hmid_lds_bytes(up, T, self.nl, esz, self.ntab > 1) > 0]
@@ -547,101 +591,117 @@ class MultigridSolver:
                 hi -= 1
         return groups
 
+    # the recurring parameter groups of the level entry points, by name (include/feanet_hip.h)
+    def _pid(self, l):
+        Lv = self.levels[l]
+        return None if Lv.pid is None else Lv.pid.data_ptr()
+
+    def _stencil(self, pid):
+        return dict(pid=pid, ktab=self.ktab.data_ptr(), omd=self.omd.data_ptr(), ntab=self.ntab)
+
+    def _restriction(self):
+        return dict(rtab=self.rtab.data_ptr(), nrtab=self.rtab.shape[0], w0=self.w[0])
+
+    def _prolongation(self):
+        return dict(ptab=self.ptab.data_ptr(), nptab=self.ptab.shape[0], w1=self.w[1])
+
+    def _hnet(self):
+        return dict(hw=self.hw.data_ptr(), nlayers=self.nl)
+
+    def _coarse_pitch(self, l):
+        """Row pitch and sample stride of level l + 1 (and of level l + 2: _coarse_pitch2)."""
+        return dict(ldc=self.levels[l + 1].ld, bstridec=self.levels[l + 1].bs)
+
+    def _coarse_pitch2(self, l):
+        return dict(ldc2=self.levels[l + 2].ld, bstridec2=self.levels[l + 2].bs)
+
     def bind_step(self, st):
         """One schedule step -> (C-ABI function base name, args without the stream)."""
         lv = self.levels
-        kt, om, nt = self.ktab.data_ptr(), self.omd.data_ptr(), self.ntab
-        rt, pt = self.rtab.data_ptr(), self.ptab.data_ptr()
-        nr, npt = self.rtab.shape[0], self.ptab.shape[0]
-
-        def pid(l):
-            return None if lv[l].pid is None else lv[l].pid.data_ptr()
+        launch, pid, sten = _lib.launch, self._pid, self._stencil
+        rest, prol, cp, cp2 = self._restriction, self._prolongation, self._coarse_pitch, self._coarse_pitch2
 
         def ptr(l, name):
             return None if name is None else self._ptr(l, name)
 
         def geom(l):
-            return lv[l].geom()
+            return lv[l].geom_kw()
 
-        def cgeom(l):
-            return (lv[l + 1].ld, lv[l + 1].bs)
+        def pids(a, n):
+            return _lib.PtrArray([pid(j) for j in range(a, a + n)]) if self.ntab > 1 else None
+
+        def fs(a, n):
+            return _lib.PtrArray([lv[j].f.data_ptr() for j in range(a, a + n)])
+
+        def tail(t):  # the LDS-resident tails take every level's pattern map and the tables without their row counts
+            return dict(Ht=lv[t].H, Wt=lv[t].W, nlev=self.L - t, ld_t=lv[t].ld, bs_t=lv[t].bs,
+                        pid_levels=None if self.tail_pid is None else self.tail_pid.data_ptr(),
+                        ktab=self.ktab.data_ptr(), omd=self.omd.data_ptr(), ntab=self.ntab, rtab=self.rtab.data_ptr(),
+                        ptab=self.ptab.data_ptr(), w0=self.w[0], w1=self.w[1], nu1=self.nu1, nu2=self.nu2, B=lv[t].B)
 
         kind, l = st[0], st[1]
         f = lv[l].f.data_ptr()
         if kind == "sweep":
-            return ("mg_sweep", (ptr(l, st[2]), f, ptr(l, st[3]), pid(l), kt, om, nt) + geom(l))
+            return launch("mg_sweep", u=ptr(l, st[2]), f=f, out=ptr(l, st[3]), **sten(pid(l)), **geom(l))
         if kind == "hsweep":
-            return ("mg_hsweep", (ptr(l, st[2]), None, f, ptr(l, st[3]), pid(l), kt, om, nt, self.hw.data_ptr(),
-                                  self.nl) + geom(l))
+            return launch("mg_hsweep", u=ptr(l, st[2]), u_raw=None, f=f, out=ptr(l, st[3]), **sten(pid(l)),
+                          **self._hnet(), **geom(l))
         if kind == "resid_restrict":
-            return ("mg_residual_restrict", (ptr(l, st[2]), f, ptr(l, st[3]), lv[l + 1].f.data_ptr(), pid(l),
-                                             kt, om, nt, rt, nr, self.w[0]) + geom(l) + cgeom(l))
+            return launch("mg_residual_restrict", u=ptr(l, st[2]), f=f, v_out=ptr(l, st[3]), fc=lv[l + 1].f.data_ptr(),
+                          **sten(pid(l)), **rest(), **geom(l), **cp(l))
         if kind == "resid_restrict2":
-            return ("mg_zero_restrict2", (f, lv[l + 1].f.data_ptr(), lv[l + 2].f.data_ptr(), pid(l), pid(l + 1),
-                                          kt, om, nt, rt, nr, self.w[0]) + geom(l) + cgeom(l) + cgeom(l + 1))
+            return launch("mg_zero_restrict2", f=f, fc=lv[l + 1].f.data_ptr(), fc2=lv[l + 2].f.data_ptr(),
+                          pidc=pid(l + 1), **sten(pid(l)), **rest(), **geom(l), **cp(l), **cp2(l))
         if kind == "sweep_restrict":
-            return ("mg_sweep_restrict", (ptr(l, st[2]), f, ptr(l, st[3]), lv[l + 1].f.data_ptr(), pid(l),
-                                          kt, om, nt, rt, nr, self.w[0]) + geom(l) + cgeom(l) + (None, None, None))
+            return launch("mg_sweep_restrict", u=ptr(l, st[2]), f=f, u_out=ptr(l, st[3]), fc=lv[l + 1].f.data_ptr(),
+                          **sten(pid(l)), **rest(), **geom(l), **cp(l), norm_ws=None, norm_hist=None, norm_cnt=None)
         if kind == "prolong_sweep":
-            return ("mg_prolong_sweep", (ptr(l, st[2]), ptr(l + 1, st[3]), f, ptr(l, st[4]), pid(l),
-                                         pid(l + 1), kt, om, nt, pt, npt, self.w[1]) + geom(l) + cgeom(l))
+            return launch("mg_prolong_sweep", u=ptr(l, st[2]), ec=ptr(l + 1, st[3]), f=f, out=ptr(l, st[4]),
+                          pidc=pid(l + 1), **sten(pid(l)), **prol(), **geom(l), **cp(l))
         if kind == "prolong_sweep2":
-            return ("mg_prolong2", (lv[l + 1].f.data_ptr(), ptr(l + 2, st[2]), f, ptr(l, st[3]), pid(l), pid(l + 1),
-                                    pid(l + 2), kt, om, nt, pt, npt, self.w[1]) + geom(l) + cgeom(l) + cgeom(l + 1))
+            return launch("mg_prolong2", fc=lv[l + 1].f.data_ptr(), ec2=ptr(l + 2, st[2]), f=f, out=ptr(l, st[3]),
+                          pidc=pid(l + 1), pidc2=pid(l + 2), **sten(pid(l)), **prol(), **geom(l), **cp(l), **cp2(l))
         if kind == "prolong_add":
-            return ("mg_prolong_add", (ptr(l, st[2]), ptr(l + 1, st[3]), ptr(l, st[4]), pid(l + 1), pt, npt,
-                                       self.w[1]) + geom(l) + cgeom(l))
+            return launch("mg_prolong_add", u=ptr(l, st[2]), ec=ptr(l + 1, st[3]), out=ptr(l, st[4]), pidc=pid(l + 1),
+                          **prol(), **geom(l), **cp(l))
         if kind == "mid_down":
             a, k, T = st[1], st[2], st[3]
-            fs = _lib.PtrArray([lv[j].f.data_ptr() for j in range(a, a + k + 1)])
-            pids = _lib.PtrArray([pid(j) for j in range(a, a + k + 1)]) if nt > 1 else None
             TR, TC = T if isinstance(T, tuple) else (T, T)
-            return ("mg_mid_down", (fs, pids, k, self.B, lv[a].H, lv[a].W, kt, om, nt, rt, nr, self.w[0], TR, TC))
+            return launch("mg_mid_down", f=fs(a, k + 1), k=k, B=self.B, H=lv[a].H, W=lv[a].W,
+                          **sten(pids(a, k + 1)), **rest(), TR=TR, TC=TC)
         if kind == "mid_up":
             a, k, csrc, dst, T = st[1:6]
-            fs = _lib.PtrArray([lv[j].f.data_ptr() for j in range(a, a + k)])
-            pids = _lib.PtrArray([pid(j) for j in range(a, a + k + 1)]) if nt > 1 else None
             TR, TC = T if isinstance(T, tuple) else (T, T)
-            return ("mg_mid_up", (fs, ptr(a + k, csrc), ptr(a, dst), pids, k, self.B, lv[a].H, lv[a].W, kt, om, nt,
-                                  pt, npt, self.w[1], TR, TC))
+            return launch("mg_mid_up", f=fs(a, k), e=ptr(a + k, csrc), out=ptr(a, dst), k=k, B=self.B, H=lv[a].H,
+                          W=lv[a].W, **sten(pids(a, k + 1)), **prol(), TR=TR, TC=TC)
         if kind == "coarse_tail":
-            t = l
-            return ("mg_coarse_tail", (lv[t].f.data_ptr(), ptr(t, st[2]), lv[t].H, lv[t].W, self.L - t, lv[t].ld,
-                                       lv[t].bs, None if self.tail_pid is None else self.tail_pid.data_ptr(),
-                                       kt, om, nt, rt, pt, self.w[0], self.w[1], self.nu1, self.nu2,
-                                       int(self.compat == "mm_interface_q2"), lv[t].B))
+            return launch("mg_coarse_tail", f_t=f, v_t=ptr(l, st[2]), q2=int(self.compat == "mm_interface_q2"),
+                          **tail(l))
         if kind == "coarse_tail_ext":
             x, t = l, l + 1
-            return ("mg_coarse_tail_ext", (f, ptr(x, st[2]), lv[x].H, lv[x].W, lv[x].ld, lv[x].bs, self.L - t, kt, om,
-                                           nt, rt, pt, self.w[0], self.w[1], lv[x].B))
+            return launch("mg_coarse_tail_ext", f_x=f, v_x=ptr(x, st[2]), Hx=lv[x].H, Wx=lv[x].W, ld_x=lv[x].ld,
+                          bs_x=lv[x].bs, nlev=self.L - t, ktab=self.ktab.data_ptr(), omd=self.omd.data_ptr(),
+                          ntab=self.ntab, rtab=self.rtab.data_ptr(), ptab=self.ptab.data_ptr(), w0=self.w[0],
+                          w1=self.w[1], B=lv[x].B)
         if kind == "hsweep_restrict":
-            return ("mg_hsweep_restrict", (ptr(l, st[2]), None, f, ptr(l, st[3]), lv[l + 1].f.data_ptr(), pid(l), kt,
-                                           om, nt, self.hw.data_ptr(), self.nl, rt, nr, self.w[0]) + geom(l) +
-                    cgeom(l))
+            return launch("mg_hsweep_restrict", u=ptr(l, st[2]), u_raw=None, f=f, out=ptr(l, st[3]),
+                          fc=lv[l + 1].f.data_ptr(), **sten(pid(l)), **self._hnet(), **rest(), **geom(l), **cp(l))
         if kind == "prolong_hsweep":
-            return ("mg_prolong_hsweep", (ptr(l, st[2]), None, ptr(l + 1, st[3]), f, ptr(l, st[4]), pid(l), pid(l + 1), kt,
-                                          om, nt, self.hw.data_ptr(), self.nl, pt, npt, self.w[1]) + geom(l) +
-                    cgeom(l))
+            return launch("mg_prolong_hsweep", u=ptr(l, st[2]), u_raw=None, ec=ptr(l + 1, st[3]), f=f,
+                          out=ptr(l, st[4]), pidc=pid(l + 1), **sten(pid(l)), **self._hnet(), **prol(), **geom(l),
+                          **cp(l))
         if kind == "hmid_down":
             a, da, da1, T = st[1:5]
-            fs = _lib.PtrArray([lv[j].f.data_ptr() for j in range(a, a + 3)])
             us = _lib.PtrArray([ptr(a, da), ptr(a + 1, da1)])
-            pids = _lib.PtrArray([pid(j) for j in range(a, a + 3)]) if nt > 1 else None
-            return ("mg_hmid_down", (fs, us, pids, self.B, lv[a].H, lv[a].W, kt, om, nt, self.hw.data_ptr(), self.nl,
-                                     rt, nr, self.w[0], T))
+            return launch("mg_hmid_down", f=fs(a, 3), u=us, B=self.B, H=lv[a].H, W=lv[a].W, **sten(pids(a, 3)),
+                          **self._hnet(), **rest(), T=T)
         if kind == "hmid_up":
             a, u0, u1, esrc, dst, T = st[1:7]
-            fs = _lib.PtrArray([lv[a].f.data_ptr(), lv[a + 1].f.data_ptr()])
             us = _lib.PtrArray([ptr(a, u0), ptr(a + 1, u1)])
-            pids = _lib.PtrArray([pid(j) for j in range(a, a + 3)]) if nt > 1 else None
-            return ("mg_hmid_up", (fs, us, ptr(a + 2, esrc), ptr(a, dst), pids, self.B, lv[a].H, lv[a].W, kt, om, nt,
-                                   self.hw.data_ptr(), self.nl, pt, npt, self.w[1], T))
+            return launch("mg_hmid_up", f=fs(a, 2), u=us, e=ptr(a + 2, esrc), out=ptr(a, dst), B=self.B, H=lv[a].H,
+                          W=lv[a].W, **sten(pids(a, 3)), **self._hnet(), **prol(), T=T)
         if kind == "hjac_tail":
-            t = l
-            return ("mg_hjac_tail", (lv[t].f.data_ptr(), ptr(t, st[2]), lv[t].H, lv[t].W, self.L - t, lv[t].ld,
-                                     lv[t].bs, None if self.tail_pid is None else self.tail_pid.data_ptr(),
-                                     kt, om, nt, rt, pt, self.hw.data_ptr(), self.nl, self.w[0], self.w[1],
-                                     self.nu1, self.nu2, lv[t].B))
+            return launch("mg_hjac_tail", f_t=f, u_t=ptr(l, st[2]), **self._hnet(), **tail(l))
         raise ValueError(f"MultigridSolver: unknown schedule step {kind!r}")
 
     def _plan(self, start):
@@ -665,34 +725,22 @@ class MultigridSolver:
         """fea_mg_cycle_join: PS(0) of the cycle whose pre-smoothed iterate is in `pre`, fused with the
         next cycle's SR(0); the new pre-smoothed iterate lands in the other buffer.  norm: also append the
         residual norm of the cycle's end iterate to the solve history (solve())."""
-        lv = self.levels
-        L0, L1 = lv[0], lv[1]
-        pid = None if L0.pid is None else L0.pid.data_ptr()
-        pidc = None if L1.pid is None else L1.pid.data_ptr()
+        L0, L1 = self.levels[0], self.levels[1]
         out = out or ("b" if pre == "a" else "a")
-        return ("mg_cycle_join", (self._ptr(0, pre), ec_ptr, L0.f.data_ptr(), self._ptr(0, out),
-                                  L1.f.data_ptr(), pid, pidc, self.ktab.data_ptr(), self.omd.data_ptr(), self.ntab,
-                                  self.ptab.data_ptr(), self.ptab.shape[0], self.rtab.data_ptr(),
-                                  self.rtab.shape[0], self.w[1], self.w[0]) + L0.geom() + (L1.ld, L1.bs) +
-                ((norm_ws, None, None) if norm_ws is not None else
-                 (self.ws.data_ptr(), self._hist.data_ptr(), self._cnt.data_ptr()) if norm else (None, None, None)))
+        if norm_ws is not None:
+            norms = dict(norm_ws=norm_ws, norm_hist=None, norm_cnt=None)
+        elif norm:
+            norms = dict(norm_ws=self.ws.data_ptr(), norm_hist=self._hist.data_ptr(), norm_cnt=self._cnt.data_ptr())
+        else:
+            norms = dict(norm_ws=None, norm_hist=None, norm_cnt=None)
+        return _lib.launch("mg_cycle_join", u=self._ptr(0, pre), ec=ec_ptr, f=L0.f.data_ptr(), u_out=self._ptr(0, out),
+                           fc=L1.f.data_ptr(), pidc=self._pid(1), **self._stencil(self._pid(0)),
+                           **self._prolongation(), **self._restriction(), **L0.geom_kw(), **self._coarse_pitch(0),
+                           **norms)
 
     def _run_segment(self, key, launches):
-        """Launch a fixed list of calls: eager the first time, then as a captured HIP graph."""
-        if not self.use_graph or self._eager_runs.get(key, 0) == 0:
-            self._eager_runs[key] = self._eager_runs.get(key, 0) + 1
-            self._launch(launches)
-            return
-        g = self._graphs.get(key)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.graph(g, stream=s):
-                self._launch(launches)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            self._graphs[key] = g
-        g.replay()
+        """Launch a fixed list of calls: eager the first time, then as a captured HIP graph (run_segment)."""
+        run_segment(self, key, launches)
 
     def joined_program(self, k):
         """vcycle(k) with joined cycle boundaries as [(segment key, launches)] plus the end buffer:
@@ -702,7 +750,7 @@ class MultigridSolver:
         s0 = self._state
         plan, _ = self._plan(s0)
         head, mid = plan[0], plan[1:-1]
-        ec_ptr = plan[-1][1][1]  # level-1 correction the finest prolongation reads (same every cycle)
+        ec_ptr = _lib.arg(plan[-1], "ec")  # level-1 correction the finest prolongation reads (same every cycle)
         prog = [(("head", s0), [head])]
         pre = other(s0)
         for _ in range(k - 1):
@@ -745,15 +793,18 @@ class MultigridSolver:
             self._pack(None, L0.c, bc=self._ab_bc)
             self._c_bc = self._ab_version
 
+    def _post_smooth(self, src, dst):
+        """Level 0's last post-smooth PS(0) (prolongation + correction + sweep, the plan's last launch) reading the
+        pre-smoothed iterate in buffer `src` and writing the cycle's end iterate to `dst`."""
+        return _lib.replace(self._plan("a")[0][-1], u=self._ptr(0, src), out=self._ptr(0, dst))
+
     def _collapse(self):
         """Leave the pipelined state: the last cycle's end iterate recomputed (PS(0) from the join's
         inputs) into the buffer of the now-discarded next pre-smooth, which becomes the resting state."""
         m = self._mid
         if m is None:
             return
-        name, args = self._plan("a")[0][-1]
-        args = (self._ptr(0, m["last"]), args[1], args[2], self._ptr(0, m["pre"])) + args[4:]
-        self._launch([(name, args)])
+        self._launch([self._post_smooth(m["last"], m["pre"])])
         self._state = m["pre"]
         self._mid = None
 
@@ -768,9 +819,7 @@ class MultigridSolver:
             return self._state
         if not m["mat"]:
             self._ensure_c()
-            name, args = self._plan("a")[0][-1]  # PS(0): (u, ec, f, out, ...)
-            args = (self._ptr(0, m["last"]), args[1], args[2], self._ptr(0, "c")) + args[4:]
-            self._launch([(name, args)])
+            self._launch([self._post_smooth(m["last"], "c")])
             m["mat"] = True
         return "c"
 
@@ -787,7 +836,7 @@ class MultigridSolver:
         other = lambda b: "b" if b == "a" else "a"
         plan, _ = self._plan("a")
         mid = plan[1:-1]  # levels >= 1 (they never touch the finest level's iterate buffers)
-        ec_ptr = plan[-1][1][1]  # level-1 correction the finest prolongation reads (same every cycle)
+        ec_ptr = _lib.arg(plan[-1], "ec")  # level-1 correction the finest prolongation reads (same every cycle)
         if self._mid is None:
             s0 = self._state
             head = [self._plan(s0)[0][0]]
@@ -816,7 +865,7 @@ class MultigridSolver:
         """Run k V-cycles on the resident iterate (asynchronous; no host sync)."""
         if k < 1:
             return
-        if self._joinable() and not getattr(self, "_hjac_first", False):
+        if self._joinable() and not self._hjac_first:
             self._vcycles_pipelined(k)
             return
         self._vcycles_plain(k)
@@ -826,33 +875,12 @@ class MultigridSolver:
         self._collapse()
         for _ in range(k):
             plan, end = self._plan(self._state)
-            if getattr(self, "_hjac_first", False):
+            if self._hjac_first:  # the first sweep of the first cycle after load() reads the un-reset iterate
                 self._hjac_first = False
-                first = list(plan)
-                # the first finest-level sweep of the cycle (its f is level 0's), whatever precedes it
-                f0 = self.levels[0].f.data_ptr()
-                for i, (name, args) in enumerate(first):
-                    fi = {"mg_hsweep": 2, "mg_hsweep_restrict": 2, "mg_prolong_hsweep": 3}.get(name)  # f's slot
-                    if fi is not None and args[fi] == f0:
-                        first[i] = (name, (args[0], self._raw.data_ptr()) + args[2:])
-                        break
-                self._launch(first)
-                self._state = end
-                continue
-            if not self.use_graph or self._eager_runs.get(self._state, 0) == 0:
-                self._eager_runs[self._state] = self._eager_runs.get(self._state, 0) + 1
-                self._launch(plan)
+                first = first_sweep_raw(plan, self.levels[0].f.data_ptr(), self._raw.data_ptr())
+                self._launch(plan if first is None else first)
             else:
-                g = self._graphs.get(self._state)
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
-                    s = torch.cuda.Stream(self.device)
-                    s.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.graph(g, stream=s):
-                        self._launch(plan)
-                    torch.cuda.current_stream(self.device).wait_stream(s)
-                    self._graphs[self._state] = g
-                g.replay()
+                self._run_segment(self._state, plan)
             self._state = end
 
     def step(self, u, f, cycles=1):
@@ -892,7 +920,7 @@ class MultigridSolver:
         if f is not None or F is not None:
             self.set_rhs(f=f, F=F)
         self.load(u0)
-        if self._joinable() and not getattr(self, "_hjac_first", False) and self.use_graph:
+        if self._joinable() and not self._hjac_first and self.use_graph:
             return self._solve_joined(eps, max_cycles, u0)
         hist = [self.residual_norm().cpu().numpy()]
         while hist[-1].max() > eps and len(hist) <= max_cycles:
@@ -915,7 +943,7 @@ class MultigridSolver:
     def _read_hist(self, r0, r1):
         """History rows r0..r1-1 to the host: one async copy into pinned memory, then a stream sync."""
         n = (r1 - r0) * self.B
-        if getattr(self, "_hist_host", None) is None or self._hist_host.numel() < self._hist.numel():
+        if self._hist_host is None or self._hist_host.numel() < self._hist.numel():
             self._hist_host = torch.empty(self._hist.numel(), dtype=torch.float64, pin_memory=True)
         out = self._hist_host[:n]
         out.copy_(self._hist[r0:r1].reshape(-1), non_blocking=True)
@@ -956,17 +984,17 @@ class MultigridSolver:
         s0 = self._state
         plan, _ = self._plan(s0)
         head, mid = plan[0], plan[1:-1]
-        ec_ptr = plan[-1][1][1]
+        ec_ptr = _lib.arg(plan[-1], "ec")
         gen = self._hist_gen
         assert head[0] == "mg_sweep_restrict", head[0]
-        hargs = head[1][:-3] + (self.ws.data_ptr(), self._hist.data_ptr(), self._cnt.data_ptr())
-        head_launch = (head[0], hargs)  # pre-smooth + initial norm (row 0): opens the first block's graph
+        # pre-smooth + initial norm (row 0): opens the first block's graph
+        head_launch = _lib.replace(head, norm_ws=self.ws.data_ptr(), norm_hist=self._hist.data_ptr(),
+                                   norm_cnt=self._cnt.data_ptr())
         self._set_cnt(0)
         S = "b" if s0 == "a" else "a"
         # deferred norms: each joined cycle of a graph block writes its partial sums to its own set, one
         # reduction launch per graph block appends the block's rows
-        esz = 4 if self.dtype == torch.float32 else 8
-        per = _lib.join_norm_parts(self.B, L0.H, L0.W, esz)
+        per = _lib.join_norm_parts(self.B, L0.H, L0.W, L0.esz)
         stride = per * self.B
         Gmax = self.SOLVE_BLOCK_MAX
         if self._sws is None or self._sws.numel() < Gmax * stride:
@@ -974,7 +1002,7 @@ class MultigridSolver:
             self._hist_gen += 1  # captured solve graphs hold the old workspace pointer
             gen = self._hist_gen
         log = self._solve_log = []
-        trace = getattr(self, "_trace", False)  # diagnostics: synchronise and time every phase
+        trace = self._trace
 
         def mark(what):
             if trace:
@@ -1002,8 +1030,8 @@ class MultigridSolver:
                 for i in range(blk):  # cycle i of the graph block: partial sums into set i
                     launches += mid + [self._join_call(p, ec_ptr, out=t, norm_ws=self._sws.data_ptr() + 8 * i * stride)]
                     last, p, t = p, t, (Y if t == X else X)
-                launches.append(("norm_append", (self._sws.data_ptr(), stride, per, self.B, blk, self._hist.data_ptr(),
-                                                 self._cnt.data_ptr())))
+                launches.append(_lib.launch("norm_append", ws=self._sws.data_ptr(), stride=stride, per=per, B=self.B,
+                                            nrows=blk, hist=self._hist.data_ptr(), cnt=self._cnt.data_ptr()))
                 self._run_segment(key, launches)
             return last, p
 
@@ -1063,9 +1091,7 @@ class MultigridSolver:
         # v of the last cycle: PS(0) from the last join's inputs (its pre-smoothed iterate `last_read`, the
         # level-1 correction untouched since), into a ping-pong buffer of the unjoined plans
         D = "b" if last_read == "a" else "a"
-        name, args = self._plan("a")[0][-1]
-        args = (self._ptr(0, last_read), args[1], args[2], self._ptr(0, D)) + args[4:]
-        self._run_segment(("tail", last_read, D), [(name, args)])
+        self._run_segment(("tail", last_read, D), [self._post_smooth(last_read, D)])
         self._state = D
         mark("tail")
         u = self.solution()
@@ -1076,7 +1102,7 @@ class MultigridSolver:
     def bytes_per_vcycle(self, k=1):
         """Algorithmic HBM bytes per V-cycle as executed (DESIGN.md §3 accounting).  Joinable solvers run
         every cycle as [levels >= 1 + one fea_mg_cycle_join] (pipelined, _vcycles_pipelined)."""
-        esz = 4 if self.dtype == torch.float32 else 8
+        esz = self.levels[0].esz
         plan = self._plan("a")[0]
         if not self._joinable():
             return self._plan_bytes(plan)
@@ -1088,31 +1114,30 @@ class MultigridSolver:
         return self._plan_bytes(plan[1:-1]) + join
 
     def _plan_bytes(self, plan):
-        esz = 4 if self.dtype == torch.float32 else 8
+        esz = self.levels[0].esz
         pb = 1 if self.problem == "interface" else 0
         total = 0
-        for name, args in plan:
+        for rec in plan:
+            name = rec[0]
             if name in ("mg_coarse_tail", "mg_hjac_tail"):
                 continue
             if name == "mg_coarse_tail_ext":  # read f_X twice (down, up), write v_X (the tail itself: LDS)
-                H, W, B = args[2], args[3], args[-1]
+                H, W, B = (_lib.arg(rec, p) for p in ("Hx", "Wx", "B"))
                 total += 3 * esz * B * (H - 2) * (W - 2)
                 continue
+            B, H, W = (_lib.arg(rec, p) for p in ("B", "H", "W"))
             if name == "mg_hsweep":  # read u (NULL: zero guess) and f (+ pattern), write out
-                B, H, W = args[-5:-2]
-                total += B * (H - 2) * (W - 2) * (esz * (3 if args[0] is not None else 2) + pb)
+                total += B * (H - 2) * (W - 2) * (esz * (3 if _lib.arg(rec, "u") is not None else 2) + pb)
                 continue
-            if name in ("mg_hsweep_restrict", "mg_prolong_hsweep"):  # (..., B, H, W, ld, bs, ldc, bsc)
-                B, H, W = args[-7:-4]
+            if name in ("mg_hsweep_restrict", "mg_prolong_hsweep"):
                 nodes = B * (H - 2) * (W - 2)
                 coarse = B * ((H + 1) // 2 - 2) * ((W + 1) // 2 - 2)
                 if name == "mg_hsweep_restrict":  # read u (or not), f; write out, f_c
-                    total += nodes * (esz * (3 if args[0] is not None else 2) + pb) + coarse * esz
+                    total += nodes * (esz * (3 if _lib.arg(rec, "u") is not None else 2) + pb) + coarse * esz
                 else:  # read u, f, e; write out
                     total += nodes * (3 * esz + pb) + coarse * (esz + pb)
                 continue
             if name in ("mg_hmid_down", "mg_hmid_up"):
-                B, H, W = args[3:6] if name == "mg_hmid_down" else args[5:8]
                 n = []
                 for _ in range(3):
                     n.append(B * (H - 2) * (W - 2))
@@ -1123,7 +1148,7 @@ class MultigridSolver:
                     total += esz * (3 * n[0] + 2 * n[1] + n[2]) + pb * (n[0] + n[1] + n[2])
                 continue
             if name in ("mg_mid_down", "mg_mid_up"):
-                k, B, H, W = args[4:8] if name == "mg_mid_up" else args[2:6]
+                k = _lib.arg(rec, "k")
                 sizes = []
                 for _ in range(k + 1):
                     sizes.append(B * (H - 2) * (W - 2))
@@ -1134,7 +1159,6 @@ class MultigridSolver:
                     total += esz * (sum(sizes) + sizes[0]) + pb * sum(sizes)
                 continue
             if name == "mg_zero_restrict2":  # read f_l (+ pattern), write f_{l+1}, f_{l+2}
-                B, H, W = args[-9:-6]
                 n0 = B * (H - 2) * (W - 2)
                 H, W = (H + 1) // 2, (W + 1) // 2
                 n1 = B * (H - 2) * (W - 2)
@@ -1142,30 +1166,25 @@ class MultigridSolver:
                 total += n0 * (esz + pb) + (n1 + n2) * esz
                 continue
             if name == "mg_prolong2":  # read f_l, f_{l+1} (+ patterns), e_{l+2}; write u_l
-                B, H, W = args[-9:-6]
                 n0 = B * (H - 2) * (W - 2)
                 H, W = (H + 1) // 2, (W + 1) // 2
                 n1 = B * (H - 2) * (W - 2)
                 n2 = B * ((H + 1) // 2 - 2) * ((W + 1) // 2 - 2)
                 total += n0 * (2 * esz + pb) + n1 * (esz + pb) + n2 * (esz + pb)
                 continue
-            if name == "mg_sweep_restrict":  # (..., B, H, W, ld, bs, ldc, bsc, norm_ws, norm_hist, norm_cnt)
-                B, H, W = args[-10:-7]
-            else:
-                B, H, W = (args[-7:-4] if name in ("mg_residual_restrict", "mg_prolong_sweep", "mg_prolong_add")
-                           else args[-5:-2])
             nodes = B * (H - 2) * (W - 2)
             coarse = B * ((H + 1) // 2 - 2) * ((W + 1) // 2 - 2)
             if name == "mg_sweep":
-                total += nodes * (esz * (3 if args[0] is not None else 2) + pb)
+                total += nodes * (esz * (3 if _lib.arg(rec, "u") is not None else 2) + pb)
             elif name == "mg_residual_restrict":
-                total += nodes * (esz * (2 if args[0] is not None else 1) + pb) + coarse * esz
-                if args[0] is None and args[2] is not None:
+                u, v_out = _lib.arg(rec, "u"), _lib.arg(rec, "v_out")
+                total += nodes * (esz * (2 if u is not None else 1) + pb) + coarse * esz
+                if u is None and v_out is not None:
                     total += nodes * esz  # v written
             elif name == "mg_sweep_restrict":
                 total += nodes * (3 * esz + pb) + coarse * esz
             elif name == "mg_prolong_sweep":  # u = NULL: the iterate is recomputed from f
-                total += nodes * ((3 if args[0] is not None else 2) * esz + pb) + coarse * (esz + pb)
+                total += nodes * ((3 if _lib.arg(rec, "u") is not None else 2) * esz + pb) + coarse * (esz + pb)
             elif name == "mg_prolong_add":
                 total += nodes * 2 * esz + coarse * (esz + pb)
         return total

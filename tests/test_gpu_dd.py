@@ -479,11 +479,12 @@ def test_restriction_send_forms_bitwise(kind, problem):
     s.set_rhs(f=torch.randn(1, 1, 513, 513, device="cuda", dtype=T, generator=g))
     stream = torch.cuda.current_stream().cuda_stream
     if kind == "zr2":
-        name, args = s.bind_step(("resid_restrict2", 0))
+        rec = s.bind_step(("resid_restrict2", 0))
         out = s.levels[2]
     else:
-        name, args = s.bind_step(("resid_restrict", 0, None, None))
+        rec = s.bind_step(("resid_restrict", 0, None, None))
         out = s.levels[1]
+    name, args = rec
     r0, r1, c0, c1 = 5, out.H, 3, 40  # a block touching the last (boundary) row
     _lib.call(name, T, *args, stream)
     ref = out.view(out.f).clone()
@@ -494,7 +495,10 @@ def test_restriction_send_forms_bitwise(kind, problem):
     if kind == "zr2":
         _lib.call("mg_zero_restrict2_send", T, *args, send.data_ptr(), r0, r1, c0, c1, stream)
     else:
-        _lib.call("mg_zero_restrict_send", T, args[1], args[3], *args[4:], send.data_ptr(), r0, r1, c0, c1, stream)
+        assert _lib.arg(rec, "u") is None and _lib.arg(rec, "v_out") is None  # the zero-guess form: both dropped
+        carried = [_lib.arg(rec, p) for p in ("f", "fc", "pid", "ktab", "omd", "ntab", "rtab", "nrtab", "w0", "B", "H",
+                                              "W", "ld", "bstride", "ldc", "bstridec")]
+        _lib.call("mg_zero_restrict_send", T, *carried, send.data_ptr(), r0, r1, c0, c1, stream)
     torch.cuda.synchronize()
     assert torch.equal(out.view(out.f), ref) and torch.equal(s.levels[1].view(s.levels[1].f), ref1)
     exp = ref[:, r0:r1, c0:c1].clone()
@@ -526,7 +530,7 @@ def test_mid_down_gathered_bitwise(grid, B, monkeypatch):
     plan, _ = s._plan("a")
     name, args = plan[0]
     assert name == "mg_mid_down", [p[0] for p in plan]
-    k = args[2]
+    k = _lib.arg(plan[0], "k")
     stream = torch.cuda.current_stream().cuda_stream
     _lib.call(name, T, *args, stream)
     refs = [s.levels[j].view(s.levels[j].f).clone() for j in range(k + 1)]

@@ -395,17 +395,18 @@ def test_hmid_api_rejects_bad_arguments():
     hw = torch.zeros(27, device="cuda", dtype=T)
     fs = _lib.PtrArray([l.f.data_ptr() for l in lv])
     us = _lib.PtrArray([lv[0].a.data_ptr(), lv[1].a.data_ptr()])
-    ok = (fs, us, None, 1, 257, 257, kt.data_ptr(), om.data_ptr(), 1, hw.data_ptr(), 3, kt.data_ptr(), 1, 1.0)
+    ok = _lib.launch("mg_hmid_down", f=fs, u=us, pid=None, B=1, H=257, W=257, ktab=kt.data_ptr(), omd=om.data_ptr(),
+                     ntab=1, hw=hw.data_ptr(), nlayers=3, rtab=kt.data_ptr(), nrtab=1, w0=1.0, T=8)
     assert _lib.hmid_lds_bytes(False, 8, 3, 8, False) > 0 and _lib.hmid_lds_bytes(False, 64, 3, 8, False) == -1
     assert _lib.hmid_lds_bytes(True, 32, 3, 8, False) > 0 and _lib.hmid_lds_bytes(True, 128, 3, 8, False) == -1
     for bad in (dict(H=256), dict(TT=64), dict(ntab=16, nr=16)):
-        args = list(ok) + [bad.get("TT", 8), None]
+        rec = _lib.replace(ok, T=bad.get("TT", 8))
         if "H" in bad:
-            args[4] = bad["H"]
+            rec = _lib.replace(rec, H=bad["H"])
         if "ntab" in bad:
-            args[8], args[12] = bad["ntab"], bad["nr"]
+            rec = _lib.replace(rec, ntab=bad["ntab"], nrtab=bad["nr"])
         with pytest.raises(RuntimeError, match="invalid arguments"):
-            _lib.call("mg_hmid_down", T, *args)
+            _lib.call("mg_hmid_down", T, *rec[1], None)
     with pytest.raises(RuntimeError, match="invalid arguments"):
         _lib.call("mg_hmid_up", T, _lib.PtrArray([lv[0].f.data_ptr(), lv[1].f.data_ptr()]), us, lv[2].a.data_ptr(),
                   lv[0].a.data_ptr(), None, 1, 257, 257, kt.data_ptr(), om.data_ptr(), 1, hw.data_ptr(), 3,

@@ -1246,6 +1246,52 @@ def test_solver_pairs_restrictions():
     assert torch.equal(outs[0], outs[1])
 
 
+# bytes_per_vcycle() of tools/plan_dump.py's single-GPU configurations.  The literals are what the positional
+# accounting printed (tools/plan_dump.py run on the commit before launch records were read by parameter name), not
+# what the code under test gives.
+_PINNED_BYTES = {
+    "poisson n=1024 fp32": 18655300,
+    "poisson n=512 fp32 MID_NODES=300000": 4594736,
+    "poisson n=32 fp64 unfused V(2,2), no tail": 141696,
+    "poisson n=32 fp64 unfused V(2,0), no tail": 101840,
+    "interface n=32 fp64 compat=mm_interface_q2": 147975,
+    "poisson n=128 fp64 zero_start": 450600,
+    "interface n=128 fp32 B=2, 16-row R/P": 490796,
+    "poisson n=256 fp32 B=64": 70584320,
+    "hjac n=256 fp32": 2043964,
+    "hjac n=512 fp32": 8377420,
+    "hjac n=32 fp64 unfused": 80480,
+}
+
+
+def test_bytes_per_vcycle_pinned(monkeypatch):
+    """The bench line's byte accounting (MultigridSolver.bytes_per_vcycle / _plan_bytes) on every configuration of
+    the plan dumper: the pinned integers, and between them the plans meet every kernel name _plan_bytes has a branch
+    for.  Builds solvers only; nothing is launched beyond construction."""
+    import inspect
+    import os
+    import re
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    from tools.plan_dump import single_gpu_cases
+    from feanet_amd.solver import MultigridSolver
+    cases = single_gpu_cases()
+    assert sorted(label for label, _, _ in cases) == sorted(_PINNED_BYTES)
+    met = set()
+    for label, make, mid_nodes in cases:
+        if mid_nodes:  # read when the plan is built
+            monkeypatch.setattr(MultigridSolver, "MID_NODES", mid_nodes)
+        s = make()
+        plan = s._plan("a")[0]
+        monkeypatch.undo()
+        met.update(name for name, _ in (plan[1:-1] if s._joinable() else plan))  # what _plan_bytes is handed
+        got = s.bytes_per_vcycle()
+        print(label, got)
+        assert got == _PINNED_BYTES[label], label
+    branches = set(re.findall(r'"(mg_[a-z0-9_]+)"', inspect.getsource(MultigridSolver._plan_bytes)))
+    assert len(branches) == 17 and branches <= met, sorted(branches - met)
+
+
 @pytest.mark.parametrize("T", [torch.float32, torch.float64])
 @pytest.mark.parametrize("problem,n,m,B", [("poisson", 8, None, 1), ("poisson", 16, None, 3), ("poisson", 64, None, 2),
                                            ("poisson", 256, None, 1), ("poisson", 512, None, 2),

@@ -35,15 +35,15 @@ s.vcycle(2)
 torch.cuda.synchronize()
 stream = torch.cuda.current_stream().cuda_stream
 buf = (ctypes.c_longlong * 4096)()
-for name, args in s._plan("a")[0]:
+for rec in s._plan("a")[0]:
+    name, args = rec
     if name not in ("mg_hmid_down", "mg_hmid_up"):
         continue
     for _ in range(5):
         _lib.call(name, T, *args, stream)
     torch.cuda.synchronize()
     _lib.lib().fea_hmid_trace_read(buf)
-    T_ = args[-1]
-    H = args[4] if name == "mg_hmid_down" else args[6]
+    T_, H = _lib.arg(rec, "T"), _lib.arg(rec, "H")
     Ht = H if name == "mg_hmid_up" else ((H + 1) // 2 + 1) // 2
     nwg = (-(-(Ht - 2) // T_)) ** 2
     st = [buf[2 * i] for i in range(nwg)]
