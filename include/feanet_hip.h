@@ -74,7 +74,8 @@ int fea_norm_append(const double* ws, long long stride, long long per, int B, in
 
 /* y = K u: y[i] = sum_d ktab[pid(i+d)][d] * u[i+d], zero padding.
  * Replaces KNet.forward (FEANet/model.py:22-30); with ntab=1, pid=NULL it is FNet.forward
- * (model.py:60-61) and one HNet layer (M-FEANet-mg_test.ipynb:104-106) too.  pid is [H, W]. */
+ * (model.py:60-61) and one HNet layer (M-FEANet-mg_test.ipynb:104-106) too.  pid is [H, W].
+ * Out of place: y == u is rejected with FEA_EINVAL (every node reads its neighbours' u). */
 int fea_knet_apply_f32(const float* u, float* y, const uint8_t* pid, const float* ktab, int ntab,
                        int B, int H, int W, void* stream);
 int fea_knet_apply_f64(const double* u, double* y, const uint8_t* pid, const double* ktab, int ntab,
@@ -86,13 +87,15 @@ int fea_split_x_f64(const double* x, double* xs, const uint8_t* pid, int C, int 
 
 /* Periodic weighted-Jacobi sweep (JacobiBlockPBC.jacobi_convolution, FEANet/jacobi.py:86-97), period
  * n = N - 1, single pattern: out (B x N x N) = omd[0] * (f(a+1, b+1) - K u_periodic(a, b)) +
- * u(a mod n, b mod n); f is the (N+2) x (N+2) forcing term (FNet of the periodic extension). */
+ * u(a mod n, b mod n); f is the (N+2) x (N+2) forcing term (FNet of the periodic extension).
+ * N >= 2 (a period of at least one node); out == u is rejected. */
 int fea_jacobi_sweep_pbc_f32(const float* u, const float* f, float* out, const float* ktab, const float* omd,
                              int B, int N, void* stream);
 int fea_jacobi_sweep_pbc_f64(const double* u, const double* f, double* out, const double* ktab,
                              const double* omd, int B, int N, void* stream);
 /* Circular extension of u[:, :-1, :-1] (period N - 1) to (N - 1 + lo + hi)^2 (lo rows/columns before):
- * pbc_boundary (jacobi.py:72-79) is lo = 1, hi = 2; reset_boundary (:81-84) is lo = 0, hi = 1. */
+ * pbc_boundary (jacobi.py:72-79) is lo = 1, hi = 2; reset_boundary (:81-84) is lo = 0, hi = 1.
+ * N >= 2, lo, hi >= 0, lo + hi <= 64. */
 int fea_pbc_pad_f32(const float* u, float* dst, int B, int N, int lo, int hi, void* stream);
 int fea_pbc_pad_f64(const double* u, double* dst, int B, int N, int lo, int hi, void* stream);
 
@@ -100,7 +103,8 @@ int fea_pbc_pad_f64(const double* u, double* dst, int B, int N, int lo, int hi, 
  *   u0 = u*geo + bc; r = f - K u0; out = (omd[pid]*r + u0)*geo + bc.
  * geo/bc: NULL = square domain (1 inside, 0 on the edge) / zero; *_bstride = elements
  * between samples (0 = broadcast).  Replaces JacobiBlock.jacobi_convolution
- * (FEANet/jacobi.py:39-47) with reset_boundary (:27-29) fused in. */
+ * (FEANet/jacobi.py:39-47) with reset_boundary (:27-29) fused in.  out == u is rejected with FEA_EINVAL
+ * (every node reads its neighbours' u); out == f is legal. */
 int fea_jacobi_sweep_f32(const float* u, const float* f, float* out, const uint8_t* pid,
                          const float* ktab, const float* omd, int ntab,
                          const float* geo, long long geo_bstride, const float* bc, long long bc_bstride,
@@ -110,7 +114,8 @@ int fea_jacobi_sweep_f64(const double* u, const double* f, double* out, const ui
                          const double* geo, long long geo_bstride, const double* bc, long long bc_bstride,
                          int B, int H, int W, void* stream);
 
-/* r = f - K u (the residual every driver forms, e.g. FEANet/multigrid.py:168). */
+/* r = f - K u (the residual every driver forms, e.g. FEANet/multigrid.py:168).  r == u is rejected with
+ * FEA_EINVAL (every node reads its neighbours' u); r == f is legal (f is read at the node itself only). */
 int fea_residual_f32(const float* u, const float* f, float* r, const uint8_t* pid, const float* ktab,
                      int ntab, int B, int H, int W, void* stream);
 int fea_residual_f64(const double* u, const double* f, double* r, const uint8_t* pid, const double* ktab,
@@ -158,7 +163,9 @@ int fea_residual_norm_f64(const double* u, const double* f, const uint8_t* pid, 
  *     (a, b) over the coarse interior (interior = 1, restriction) or all coarse nodes (0,
  *     prolongation); ch_c = ch when c_split else 0, ch_f likewise; gw is [C, 9]; ws holds
  *     fea_transfer_weight_grad_ws_bytes(C, B, Hc, Wc) bytes; fixed-order (deterministic) sums.
- *     Restriction weights: cf = g, ff = x (split).  Prolongation weights: cf = e (split), ff = g. */
+ *     Restriction weights: cf = g, ff = x (split).  Prolongation weights: cf = e (split), ff = g.
+ * knet_apply_adj and jacobi_sweep_adj read g at the neighbours of a node: out == g, gu == g and gf == g are
+ * rejected with FEA_EINVAL. */
 int fea_knet_apply_adj_f32(const float* g, float* out, const uint8_t* pid, const float* ktab, int ntab,
                            int B, int H, int W, void* stream);
 int fea_knet_apply_adj_f64(const double* g, double* out, const uint8_t* pid, const double* ktab, int ntab,

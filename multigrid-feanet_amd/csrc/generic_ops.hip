@@ -535,7 +535,7 @@ static const dim3 kBlock(kBX, kBY);
 
 template <typename T>
 static int knet_apply(const T* u, T* y, const uint8_t* pid, const T* ktab, int ntab, int B, int H, int W, void* stream) {
-  if (!u || !y || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W)) return FEA_EINVAL;
+  if (!u || !y || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W) || y == u) return FEA_EINVAL;
   k_knet<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(u, y, pid, ktab, ntab, H, W);
   return launch_status();
 }
@@ -559,14 +559,14 @@ static int jacobi_sweep(const T* u, const T* f, T* out, const uint8_t* pid, cons
 
 template <typename T>
 static int jacobi_sweep_pbc(const T* u, const T* f, T* out, const T* ktab, const T* omd, int B, int N, void* stream) {
-  if (!u || !f || !out || !ktab || !omd || out == u || bad_shape(B, N, N)) return FEA_EINVAL;
+  if (!u || !f || !out || !ktab || !omd || out == u || bad_shape(B, N, N) || N < 2) return FEA_EINVAL;
   k_jacobi_pbc<T><<<grid_for(N, N, B), kBlock, 0, (hipStream_t)stream>>>(u, f, out, ktab, omd, N);
   return launch_status();
 }
 
 template <typename T>
 static int pbc_pad(const T* u, T* dst, int B, int N, int lo, int hi, void* stream) {
-  if (!u || !dst || lo < 0 || hi < 0 || lo + hi > 64 || bad_shape(B, N, N)) return FEA_EINVAL;
+  if (!u || !dst || lo < 0 || hi < 0 || lo + hi > 64 || bad_shape(B, N, N) || N < 2) return FEA_EINVAL;
   const int M = N - 1 + lo + hi;
   k_pbc_pad<T><<<grid_for(M, M, B), kBlock, 0, (hipStream_t)stream>>>(u, dst, N, lo, M);
   return launch_status();
@@ -575,7 +575,8 @@ static int pbc_pad(const T* u, T* dst, int B, int N, int lo, int hi, void* strea
 template <typename T>
 static int residual(const T* u, const T* f, T* r, const uint8_t* pid, const T* ktab, int ntab, int B, int H, int W,
                     void* stream) {
-  if (!u || !f || !r || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W)) return FEA_EINVAL;
+  // r == u would race with the neighbours' 3x3 reads of u; r == f is pointwise and legal
+  if (!u || !f || !r || !ktab || !ntab_ok(ntab) || bad_shape(B, H, W) || r == u) return FEA_EINVAL;
   k_residual<T><<<grid_for(H, W, B), kBlock, 0, (hipStream_t)stream>>>(u, f, r, pid, ktab, ntab, H, W);
   return launch_status();
 }
