@@ -160,9 +160,7 @@ __global__ __launch_bounds__(256) void k_mg_sweep(MgArgs<T> g) {
       T o[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const T acc = kapply<T, V, MULTI>(w0, w1, w2, p0, p1, p2, k, ks, tab);
-        const T omk = MULTI ? tabv(tab, p1.a[k + 1], 9) : om;
-        o[k] = omk * (fx[k] - acc) + w1.a[k + 1];
+        o[k] = jacobi<T, V, MULTI>(w0, w1, w2, p0, p1, p2, k, fx[k], ks, om, tab);
       }
       store_masked<T, V, NT>(ob + rowo(r) + V * lane, o, cl, W);
       w0 = w1;
@@ -346,28 +344,7 @@ __global__ __launch_bounds__(256) void k_mg_resid_restrict(MgArgs<T> g) {
     T o[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      T acc;
-      if constexpr (!MULTI) {
-        acc = rs[0] * Ra[2 * q];
-        acc += rs[1] * Ra[2 * q + 1];
-        acc += rs[2] * Ra[2 * q + 2];
-        acc += rs[3] * Rb[2 * q];
-        acc += rs[4] * Rb[2 * q + 1];
-        acc += rs[5] * Rb[2 * q + 2];
-        acc += rs[6] * Rc[2 * q];
-        acc += rs[7] * Rc[2 * q + 1];
-        acc += rs[8] * Rc[2 * q + 2];
-      } else {
-        acc = tabv(rtb, Pa.a[2 * q + 1], 0) * Ra[2 * q];
-        acc += tabv(rtb, Pa.a[2 * q + 2], 1) * Ra[2 * q + 1];
-        acc += tabv(rtb, Pa.a[2 * q + 3], 2) * Ra[2 * q + 2];
-        acc += tabv(rtb, Pb.a[2 * q + 1], 3) * Rb[2 * q];
-        acc += tabv(rtb, Pb.a[2 * q + 2], 4) * Rb[2 * q + 1];
-        acc += tabv(rtb, Pb.a[2 * q + 3], 5) * Rb[2 * q + 2];
-        acc += tabv(rtb, Pc.a[2 * q + 1], 6) * Rc[2 * q];
-        acc += tabv(rtb, Pc.a[2 * q + 2], 7) * Rc[2 * q + 1];
-        acc += tabv(rtb, Pc.a[2 * q + 3], 8) * Rc[2 * q + 2];
-      }
+      const T acc = restrict9<T, MULTI>(rs, rtb, Ra, Rb, Rc, 2 * q, Pa.a, Pb.a, Pc.a, 2 * q + 1);
       o[q] = w0 * acc;
     }
     T* cp = cb + (long long)(I + 1) * g.ldc;
@@ -548,14 +525,7 @@ __device__ __forceinline__ void sweep_restrict_task(const MgArgs<T>& g, const Ta
 #pragma unroll
     for (int q = 0; q < Q; ++q) o[q] = w0 * acc[q];
     if (!own) return;
-    T* cp = cb + (long long)(I + 1) * g.ldc;
-    if (J0 + Q - 1 <= Wc - 2) {
-      vstore<T, Q>(cp, o);
-    } else {
-#pragma unroll
-      for (int q = 0; q < Q; ++q)
-        if (J0 + q <= Wc - 2) cp[q] = o[q];
-    }
+    store_masked<T, Q, false>(cb + (long long)(I + 1) * g.ldc, o, J0, Wc);
   };
 
   const int ya = 2 * I0 - 1;  // first residual row
@@ -734,39 +704,11 @@ __global__ __launch_bounds__(256) void k_mg_zero_restrict(MgArgs<T> g) {
     T o[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      T acc;
-      if constexpr (!MULTI) {
-        acc = rs[0] * Ra[2 * q];
-        acc += rs[1] * Ra[2 * q + 1];
-        acc += rs[2] * Ra[2 * q + 2];
-        acc += rs[3] * Rb[2 * q];
-        acc += rs[4] * Rb[2 * q + 1];
-        acc += rs[5] * Rb[2 * q + 2];
-        acc += rs[6] * Rc[2 * q];
-        acc += rs[7] * Rc[2 * q + 1];
-        acc += rs[8] * Rc[2 * q + 2];
-      } else {
-        acc = tabv(rtb, Pa.a[2 * q + 1], 0) * Ra[2 * q];
-        acc += tabv(rtb, Pa.a[2 * q + 2], 1) * Ra[2 * q + 1];
-        acc += tabv(rtb, Pa.a[2 * q + 3], 2) * Ra[2 * q + 2];
-        acc += tabv(rtb, Pb.a[2 * q + 1], 3) * Rb[2 * q];
-        acc += tabv(rtb, Pb.a[2 * q + 2], 4) * Rb[2 * q + 1];
-        acc += tabv(rtb, Pb.a[2 * q + 3], 5) * Rb[2 * q + 2];
-        acc += tabv(rtb, Pc.a[2 * q + 1], 6) * Rc[2 * q];
-        acc += tabv(rtb, Pc.a[2 * q + 2], 7) * Rc[2 * q + 1];
-        acc += tabv(rtb, Pc.a[2 * q + 3], 8) * Rc[2 * q + 2];
-      }
+      const T acc = restrict9<T, MULTI>(rs, rtb, Ra, Rb, Rc, 2 * q, Pa.a, Pb.a, Pc.a, 2 * q + 1);
       o[q] = w0 * acc;
     }
     if (own) {
-      T* cp = cb + (long long)(I + 1) * g.ldc;
-      if (J0 + Q - 1 <= Wc - 2) {
-        vstore<T, Q>(cp, o);
-      } else {
-#pragma unroll
-        for (int q = 0; q < Q; ++q)
-          if (J0 + q <= Wc - 2) cp[q] = o[q];
-      }
+      store_masked<T, Q, false>(cb + (long long)(I + 1) * g.ldc, o, J0, Wc);
       if (g.gsend) {
 #pragma unroll
         for (int q = 0; q < Q; ++q)
@@ -1282,9 +1224,7 @@ __global__ __launch_bounds__(256) void k_mg_prolong(MgArgs<T> g) {
     if constexpr (SWEEP) {
 #pragma unroll
       for (int k = 0; k < V; ++k) {
-        const T acc = kapply<T, V, MULTI>(a, b, c, pa, pbb, pc, k, ks, tab);
-        const T omk = MULTI ? tabv(tab, pbb.a[k + 1], 9) : om;
-        o[k] = omk * (fv[k] - acc) + b.a[k + 1];
+        o[k] = jacobi<T, V, MULTI>(a, b, c, pa, pbb, pc, k, fv[k], ks, om, tab);
       }
     } else {
 #pragma unroll
@@ -1514,9 +1454,7 @@ __global__ __launch_bounds__(256) void k_mg_prolong_zu_ovl(MgArgs<T> g) {
     T o[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const T acc = kapply<T, V, MULTI>(a.x, b.x, c.x, a.p, b.p, c.p, k, ks, tab);
-      const T omk = MULTI ? tabv(tab, b.p.a[k + 1], 9) : om;
-      o[k] = omk * (b.f[k] - acc) + b.x.a[k + 1];
+      o[k] = jacobi<T, V, MULTI>(a.x, b.x, c.x, a.p, b.p, c.p, k, b.f[k], ks, om, tab);
     }
     if (own) store_masked<T, V, NT>(ob + rowo(y), o, cl, W);
   };
@@ -1708,9 +1646,7 @@ __device__ __forceinline__ void prolong2_task(const MgArgs<T>& g, const TaskId& 
     T o[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      const T acc = kapply<T, Q, MULTI>(a_.x, b_.x, c_.x, a_.p, b_.p, c_.p, q, ks, tab);
-      const T omk = MULTI ? tabv(tab, b_.p.a[q + 1], 9) : om;
-      const T u = omk * (b_.f[q] - acc) + b_.x.a[q + 1];
+      const T u = jacobi<T, Q, MULTI>(a_.x, b_.x, c_.x, a_.p, b_.p, c_.p, q, b_.f[q], ks, om, tab);
       o[q] = (ain && jin[q]) ? u : T(0);
     }
     CRow<T, V> c{};
@@ -1779,9 +1715,7 @@ __device__ __forceinline__ void prolong2_task(const MgArgs<T>& g, const TaskId& 
     T o[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const T acc = kapply<T, V, MULTI>(a.x, b.x, c.x, a.p, b.p, c.p, k, ks, tab);
-      const T omk = MULTI ? tabv(tab, b.p.a[k + 1], 9) : om;
-      o[k] = omk * (b.f[k] - acc) + b.x.a[k + 1];
+      o[k] = jacobi<T, V, MULTI>(a.x, b.x, c.x, a.p, b.p, c.p, k, b.f[k], ks, om, tab);
     }
     if (own) store_masked<T, V, false>(ob + rowo(y), o, cl, W);
   };
@@ -2214,14 +2148,7 @@ __device__ __forceinline__ void join_task(const MgArgs<T>& g, const JoinTask& jt
           const int yr = y - 3 * S;
           auto put = [&](int I, const T (&o)[Q]) {
             if (own) {
-              T* cp = cb + (long long)(I + 1) * ldc;
-              if (J0 + Q - 1 <= Wcs - 2) {
-                vstore<T, Q>(cp, o);
-              } else {
-#pragma unroll
-                for (int q = 0; q < Q; ++q)
-                  if (J0 + q <= Wcs - 2) cp[q] = o[q];
-              }
+              store_masked<T, Q, false>(cb + (long long)(I + 1) * ldc, o, J0, Wcs);
             }
           };
           if constexpr (!REV) {

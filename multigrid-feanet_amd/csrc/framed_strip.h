@@ -1,6 +1,7 @@
 // framed_strip.h — the strip helpers of the framed level kernels (framed_ops.hip, pcg_ops.hip): the framed
-// layout, 16-byte row loads with DPP neighbours, the 3-row stencil window (kapply), the task decode, the
-// coefficient tables in LDS and the launch geometry.  Layout and work decomposition: see framed_ops.hip.
+// layout, 16-byte row loads with DPP neighbours, the 3-row stencil window (kapply) and the Jacobi emit on it
+// (jacobi), the 9-tap restriction (restrict9), the masked row store, the task decode, the coefficient tables in
+// LDS and the launch geometry.  Layout and work decomposition: see framed_ops.hip.
 #pragma once
 #include <cstdlib>
 
@@ -224,6 +225,51 @@ __device__ __forceinline__ T kapply(const Row<T, V>& w0, const Row<T, V>& w1, co
   return acc;
 }
 
+// One Jacobi-swept value, omd (f - K x) + x, at own column k of the window rows a, b, c (the shared emit of the
+// sweep, the prolongation kernels and the two-level prolongation's coarse stage).  The last line is one source
+// expression on purpose: -ffp-contract=on fuses within an expression only, so splitting it changes the bits.
+template <typename T, int N, bool MULTI>
+__device__ __forceinline__ T jacobi(const Row<T, N>& a, const Row<T, N>& b, const Row<T, N>& c, const PRow<N>& pa,
+                                    const PRow<N>& pb, const PRow<N>& pc, int k, T f, const T (&ks)[9], T om,
+                                    const T* tab) {
+  const T acc = kapply<T, N, MULTI>(a, b, c, pa, pb, pc, k, ks, tab);
+  const T omk = MULTI ? tabv(tab, pb.a[k + 1], 9) : om;
+  return omk * (f - acc) + b.a[k + 1];
+}
+
+// Coarse value of the 9-tap restriction from three residual rows in grid order: the sum over (ky, kx) of
+// R[ky][kx] r_ky[o + kx], nine statements in this order (each product fuses with its own add only).  MULTI: each
+// tap with the weight of its fine node's pattern; pa, pb, pc hold the rows' table-row offsets, the same columns
+// from index po on.
+template <typename T, bool MULTI, int NR, int NP>
+__device__ __forceinline__ T restrict9(const T (&rs)[9], const T* rtb, const T (&ra)[NR], const T (&rb)[NR],
+                                       const T (&rc)[NR], int o, const int (&pa)[NP], const int (&pb)[NP],
+                                       const int (&pc)[NP], int po) {
+  T acc;
+  if constexpr (!MULTI) {
+    acc = rs[0] * ra[o];
+    acc += rs[1] * ra[o + 1];
+    acc += rs[2] * ra[o + 2];
+    acc += rs[3] * rb[o];
+    acc += rs[4] * rb[o + 1];
+    acc += rs[5] * rb[o + 2];
+    acc += rs[6] * rc[o];
+    acc += rs[7] * rc[o + 1];
+    acc += rs[8] * rc[o + 2];
+  } else {
+    acc = tabv(rtb, pa[po], 0) * ra[o];
+    acc += tabv(rtb, pa[po + 1], 1) * ra[o + 1];
+    acc += tabv(rtb, pa[po + 2], 2) * ra[o + 2];
+    acc += tabv(rtb, pb[po], 3) * rb[o];
+    acc += tabv(rtb, pb[po + 1], 4) * rb[o + 1];
+    acc += tabv(rtb, pb[po + 2], 5) * rb[o + 2];
+    acc += tabv(rtb, pc[po], 6) * rc[o];
+    acc += tabv(rtb, pc[po + 1], 7) * rc[o + 1];
+    acc += tabv(rtb, pc[po + 2], 8) * rc[o + 2];
+  }
+  return acc;
+}
+
 template <typename T>
 struct MgArgs {
   const T* u;
@@ -311,6 +357,8 @@ __device__ __forceinline__ void load_tables(T* tab, const T* ktab, const T* omd,
     }
 }
 
+// V values of one row, columns cl .. cl+V-1, of a grid W columns wide: one vector store, or the columns left of the
+// boundary column W-1 one by one.  Fine rows (V = VEC, the level's W) and restricted rows (V = VEC/2, Wc) alike.
 template <typename T, int V, bool NT>
 __device__ __forceinline__ void store_masked(T* p, const T (&o)[V], int cl, int W) {
   if (cl + V - 1 <= W - 2) {
