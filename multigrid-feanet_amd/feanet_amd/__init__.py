@@ -3,6 +3,7 @@
   feanet_amd.ops          tensor-level HIP operators (KNet apply, Jacobi sweep, R, P, norms)
   feanet_amd.solver       MultigridSolver: fused-kernel V-cycle over framed level buffers
   feanet_amd.pcg          PCGSolver: conjugate gradients preconditioned by that V-cycle
+  feanet_amd.graphs       GraphCache: eager once, captured as a HIP graph the second time, replayed after
   feanet_amd.mesh_setup  vectorised discretisation tables (pattern maps, stencils)
   FEANet.*                drop-in modules with the reference's names (sibling package)
 """

@@ -34,12 +34,17 @@ regions of one exchange are packed into one staging buffer by one kernel (fea_dd
 message per neighbour and unpacked by one kernel (row slabs: contiguous rows, sent in place).  D0 and D1 are the
 smallest depths for which the validity simulation keeps every owned node exact.
 """
+import ctypes
+import itertools
 import os
+from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib, mesh_setup as ms, ops
-from .schedule import hjac_schedule, pair_prolongations, pair_restrictions, vcycle_schedule
+from .graphs import GraphCache
+from .schedule import _other, hjac_schedule, pair_prolongations, pair_restrictions, vcycle_schedule
 from .solver import MultigridSolver, first_sweep_raw
 
 
@@ -252,11 +257,10 @@ def simulate_validity(program, Ld, ghost, init=None, nl=0):
                 return False
         elif k == "join":
             pre, ec = st[1], st[2]
-            other = "b" if pre == "a" else "a"
             x = min(get(0, pre), 2 * get(1, ec) - 1)
             post = min(x - 1, get(0, "f"))
             nxt = min(post - 1, get(0, "f"))
-            if post < 0 or not put(0, other, nxt) or not put(1, "f", _restricted(min(nxt - 1, get(0, "f")))):
+            if post < 0 or not put(0, _other(pre), nxt) or not put(1, "f", _restricted(min(nxt - 1, get(0, "f")))):
                 return False
         else:
             raise ValueError(f"simulate_validity: unknown step {st!r}")
@@ -310,8 +314,7 @@ def _joined_chunk_steps(Ld, nu1, nu2, fuse, kind, s, D):
     >= 1, then the last PS(0).  Returns (steps, state after the chunk) with the cycle join as
     ("join", pre, ec) (ec = the level-1 correction buffer)."""
     D0, D1 = D
-    other = lambda x: "b" if x == "a" else "a"
-    s0 = s if kind == "head" else other(s)  # the start buffer of the cycle the chunk belongs to
+    s0 = s if kind == "head" else _other(s)  # the start buffer of the cycle the chunk belongs to
     steps, _ = dd_schedule(Ld, nu1, nu2, fuse, s0, D)
     ps0 = max(i for i, st in enumerate(steps) if st[0] == "prolong_sweep" and st[1] == 0)
     body = [st for st in steps[1:ps0] if st[0] != "exchange" or st[1] != 0]
@@ -319,17 +322,17 @@ def _joined_chunk_steps(Ld, nu1, nu2, fuse, kind, s, D):
     while i_mid < len(body) and body[i_mid][0] == "exchange":
         i_mid += 1
     if kind == "head":
-        ex = [("exchange", 0, other(s), D0)] + body[:i_mid]
-        return [steps[0]] + ex, other(s)
+        ex = [("exchange", 0, _other(s), D0)] + body[:i_mid]
+        return [steps[0]] + ex, _other(s)
     mid = body[i_mid:]
     if kind == "join":
         ec = steps[ps0][3]
-        last = [("join", s, ec), ("exchange", 0, other(s), D0)]
+        last = [("join", s, ec), ("exchange", 0, _other(s), D0)]
         if Ld >= 2:
             last.append(("exchange", 1, "f", D1))
-        return mid + last, other(s)
+        return mid + last, _other(s)
     ps = steps[ps0]
-    return mid + [ps, ("exchange", 0, ps[4], D0)], other(s)
+    return mid + [ps, ("exchange", 0, ps[4], D0)], _other(s)
 
 
 def _joined(nu1, nu2, fuse, smoother="jac"):
@@ -357,6 +360,36 @@ def _partition_for(m, n, P, Ld, nu1=1, nu2=1, fuse=True, grid=None, smoother="ja
         except ValueError as e:
             err = e
     raise ValueError(f"DD: no {Pr} x {Pc} partition of a {m} x {n} grid with Ld = {Ld}: {err}")
+
+
+# A chunk's segments (DDSolver.chunk): kernel segments and the communication steps between them.  Consumers test the
+# type and read the fields by name; nothing indexes a segment by position.
+@dataclass(slots=True)
+class Kernels:
+    """Launches issued back to back (one graph launch).  lvl0: one of them touches level 0, so a level-0 halo
+    exchange still in flight completes before the segment."""
+    launches: list
+    lvl0: bool = False
+
+
+@dataclass(slots=True)
+class Exchanges:
+    """One batch of halo exchanges, items = [(level, buffer, depth)].  packed: the pack into the staging buffer ran
+    at the end of the kernel segment before (the communicator's halo_pack)."""
+    items: list
+    packed: bool = False
+
+
+@dataclass(slots=True)
+class Gather:
+    """The level-Ld all-gather.  folded: the staging copy and the placement run inside the kernel segments around it."""
+    folded: bool = False
+
+
+@dataclass(slots=True)
+class Scatter:
+    """This rank's block of the coarse solution copied into level Ld's buffer `dst` as a step of its own."""
+    dst: str
 
 
 def _launch_list(launches, dtype, stream):
@@ -387,8 +420,6 @@ def _rect_records(dst, src):
     [n, 6]): the columns are the dimension of unit stride in both, the rows the largest other dimension, one
     rectangle per index of the remaining ones.  None when the views do not decompose so (no unit-stride
     dimension in common, a row pitch below the row length, different dtypes or devices)."""
-    import itertools
-    import numpy as np
     if dst.shape != src.shape or dst.dtype != src.dtype or dst.device != src.device or dst.numel() == 0:
         return None
     dims = [k for k in range(dst.dim()) if dst.shape[k] > 1]
@@ -546,7 +577,11 @@ class DDSolver:
         # _gathered_form) instead of as copy launches of their own
         self.fold_gather = fold_gather
         self._segs = {}
-        self._graphs = {}
+        # thread-local capture: the communicator's own threads (the NCCL watchdog) keep running
+        self._graphs = GraphCache(self.device, mode="thread_local")
+        self._comm_plans = {}  # a communicator's exchange plans (views of this solver's buffers), keyed by it
+        self._rect_arrays = {}  # split_join: the border / interior rectangles as the join kernel reads them
+        self._side = None  # split_join: the stream the border join and the exchange run on
         self._state = "a"
         self._raw = None  # smoother="hjac": the un-reset initial iterate the first cycle after load() reads
         self._hjac_first = False
@@ -642,84 +677,110 @@ class DDSolver:
 
     # ------------------------------------------------------------------ plan
     def _segs_of(self, steps):
-        """Kernel steps -> [("k", launches, touches_level0) | ("c", comm step, False)], consecutive
-        kernels merged into one segment (one graph launch); segments that touch level 0 are flagged, so
-        the level-0 halo exchange completes only before them (vcycle) — behind the coarse-level
-        segments and the all-gather in front of them."""
+        """Kernel steps -> [Kernels | Exchanges | Gather | Scatter], as a composition of passes: consecutive kernels
+        merged into one segment (one graph launch); segments that touch level 0 are flagged, so the level-0 halo
+        exchange completes only before them (vcycle) — behind the coarse-level segments and the all-gather in front
+        of them."""
+        segs = self._segments(self._elide_scatter(self._pair_levels(steps)))
+        if self.comm is not None and hasattr(self.comm, "halo_pack"):  # a communicator with a device pack
+            segs = self._fold_halo_pack(self._fold_gather(segs))
+        for seg in segs:
+            if isinstance(seg, Kernels):
+                seg.launches = _as_rect_copies(seg.launches)
+        return segs
+
+    def _pair_levels(self, steps):
+        """Two-level launches on the distributed levels between the communication steps (same per-level
+        computations on the same local nodes, so the ghost validity of every step is unchanged)."""
+        if not self.local.pair_levels:
+            return steps
+        ok = lambda l: l >= 1 and l + 2 <= self.Ld
+        return pair_prolongations(pair_restrictions(steps, ok), ok, finest_first=False)
+
+    def _elide_scatter(self, steps):
+        """("scatter", dst) followed by a step that can read the coarse solution in place (_scatter_direct) ->
+        that step as ("prolong_sweep2_coarse", ...), the scatter dropped."""
+        out, i = [], 0
+        while i < len(steps):
+            st, nxt = steps[i], steps[i + 1] if i + 1 < len(steps) else None
+            if st[0] == "scatter" and self._scatter_direct(st, nxt):
+                out.append(("prolong_sweep2_coarse",) + tuple(nxt[1:]))
+                i += 2
+            else:
+                out.append(st)
+                i += 1
+        return out
+
+    def _launches_of(self, st):
+        """The launches of one step that is not a communication step."""
+        if st[0] == "gather":  # one rank: the all-gather is a device copy
+            return [("copy", (self.gather_target(), self.gather_source()))]
+        if st[0] == "scatter":  # a device copy, captured with the kernels around it
+            return [("copy", self.scatter_views(st[1]))]
+        if st[0] == "coarse":
+            return list(self.coarse_plan)
+        if st[0] == "join":
+            return [self.local._join_call(st[1], self.local._ptr(1, st[2]))]
+        if st[0] == "prolong_sweep2_coarse":
+            return [self._read_coarse_in_place(self.local.bind_step(("prolong_sweep2",) + st[1:]))]
+        return [self.local.bind_step(st)]
+
+    def _segments(self, steps):
+        """Steps -> segments: consecutive kernel steps merged, consecutive exchanges as one batch of P2P ops (none
+        on one rank, which has no neighbours), the all-gather a step of its own on several ranks."""
         segs = []
-        fold = self.comm is not None and hasattr(self.comm, "halo_pack")
-        place = None  # the gathered blocks' placement, folded into the next kernel segment
-        if self.local.pair_levels:
-            # two-level launches on the distributed levels between the communication steps (same per-level
-            # computations on the same local nodes, so the ghost validity of every step is unchanged)
-            ok = lambda l: l >= 1 and l + 2 <= self.Ld
-            steps = pair_prolongations(pair_restrictions(steps, ok), ok, finest_first=False)
-        direct = None  # ("scatter", dst) folded into the next launch: it reads the coarse solution in place
-        for si, st in enumerate(steps):
-            if st[0] == "scatter" and self._scatter_direct(st, steps[si + 1] if si + 1 < len(steps) else None):
-                direct = st
-                continue
-            if st[0] == "exchange":  # consecutive exchanges go out as one batch of P2P ops
+        for st in steps:
+            if st[0] == "exchange":
                 if self.P == 1:
-                    continue  # no neighbours
-                if segs and segs[-1][0] == "c" and segs[-1][1][0] == "exchanges":
-                    segs[-1][1][1].append(st[1:])
+                    continue
+                if segs and isinstance(segs[-1], Exchanges):
+                    segs[-1].items.append(st[1:])
                 else:
-                    segs.append(("c", ("exchanges", [st[1:]]), False))
+                    segs.append(Exchanges([st[1:]]))
                 continue
             if st[0] == "gather" and self.P > 1:
-                if fold and self.Pc > 1 and segs and segs[-1][0] == "k":
-                    # 2-D blocks: the owned block goes to the all-gather's send buffer and the gathered blocks into
-                    # the coarse f.  Both fold into the launches around the all-gather where those are the zero-
-                    # guess restriction that computes f_Ld (its _send form stores the block too) and the coarse
-                    # plan's mid_down (its _gathered form reads the blocks and places them); otherwise a staging
-                    # copy ends the kernel segment before the all-gather and a placement copy starts the one after.
-                    tgt = self.gather_target()
-                    sent = self._send_form(segs[-1][1][-1]) if self.fold_gather else None
-                    if sent is not None:
-                        segs[-1][1][-1] = sent
-                    else:
-                        segs[-1][1].append(("copy", (self._gsend, self.gather_source())))
-                    place = ("place", self.gather_place_views(tgt))
-                    segs.append(("c", ("gather", True), False))
-                else:
-                    segs.append(("c", st, False))
+                segs.append(Gather())
                 continue
             lvl0 = st[0] == "join" or (st[0] not in ("gather", "scatter", "coarse") and st[1] == 0)
-            if st[0] == "gather":  # one rank: the all-gather is a device copy
-                launches = [("copy", (self.gather_target(), self.gather_source()))]
-            elif st[0] == "scatter":  # a device copy, captured with the kernels around it
-                launches = [("copy", self.scatter_views(st[1]))]
-            elif st[0] == "coarse":
-                launches = list(self.coarse_plan)
-            elif st[0] == "join":
-                launches = [self.local._join_call(st[1], self.local._ptr(1, st[2]))]
+            if not (segs and isinstance(segs[-1], Kernels)):
+                segs.append(Kernels([]))
+            segs[-1].launches.extend(self._launches_of(st))
+            segs[-1].lvl0 = segs[-1].lvl0 or lvl0
+        return segs
+
+    def _fold_gather(self, segs):
+        """2-D blocks: the owned block goes to the all-gather's send buffer and the gathered blocks into the coarse
+        f.  Both fold into the launches around the all-gather where those are the zero-guess restriction that
+        computes f_Ld (its _send form stores the block too) and the coarse plan's mid_down (its _gathered form reads
+        the blocks and places them); otherwise a staging copy ends the kernel segment before the all-gather and a
+        placement copy starts the one after."""
+        for i, seg in enumerate(segs):
+            if not (isinstance(seg, Gather) and self.Pc > 1 and i > 0 and isinstance(segs[i - 1], Kernels)):
+                continue
+            before, after = segs[i - 1].launches, segs[i + 1].launches  # the coarse solve follows every gather
+            tgt = self.gather_target()
+            sent = self._send_form(before[-1]) if self.fold_gather else None
+            if sent is not None:
+                before[-1] = sent
             else:
-                launches = [self.local.bind_step(st)]
-                if direct is not None:
-                    launches, direct = [self._read_coarse_in_place(launches[0])], None
-            if place is not None:
-                gath = self._gathered_form(launches[0]) if self.fold_gather else None
-                if gath is not None:
-                    launches = [gath] + launches[1:]
-                else:
-                    launches = [("copy", place[1])] + launches
-                place = None
-            if segs and segs[-1][0] == "k":
-                segs[-1][1].extend(launches)
-                if lvl0:
-                    segs[-1] = ("k", segs[-1][1], True)
+                before.append(("copy", (self._gsend, self.gather_source())))
+            gath = self._gathered_form(after[0]) if self.fold_gather else None
+            if gath is not None:
+                after[0] = gath
             else:
-                segs.append(("k", launches, lvl0))
-        if fold:
-            # each exchange batch's pack (TorchComm.halo_pack: one kernel) ends the kernel segment before it
-            for i, (kind, st, _) in enumerate(segs):
-                if kind == "c" and st[0] == "exchanges" and i > 0 and segs[i - 1][0] == "k":
-                    f = self.comm.halo_pack(self, *_split_exchanges(st[1], self.overlap_l0))
-                    if f is not None:
-                        segs[i - 1][1].append(("fn", f))
-                    segs[i] = ("c", ("exchanges", st[1], True), False)
-        return [(kind, _as_rect_copies(st), lvl0) if kind == "k" else (kind, st, lvl0) for kind, st, lvl0 in segs]
+                after.insert(0, ("copy", self.gather_place_views(tgt)))
+            seg.folded = True
+        return segs
+
+    def _fold_halo_pack(self, segs):
+        """Each exchange batch's pack (TorchComm.halo_pack: one kernel) ends the kernel segment before it."""
+        for before, seg in zip(segs, segs[1:]):
+            if isinstance(seg, Exchanges) and isinstance(before, Kernels):
+                f = self.comm.halo_pack(self, *_split_exchanges(seg.items, self.overlap_l0))
+                if f is not None:
+                    before.launches.append(("fn", f))
+                seg.packed = True
+        return segs
 
     def _send_form(self, launch):
         """The _send form of the zero-guess restriction `launch` when it computes f_Ld (2-D blocks: it then also
@@ -798,12 +859,12 @@ class DDSolver:
         MultigridSolver._vcycles_plain does for the first cycle after load() (solver.first_sweep_raw)."""
         f0 = self.local.levels[0].f.data_ptr()
         out, done = [], False
-        for kind, launches, lvl0 in segs:
-            if kind == "k" and not done:
-                first = first_sweep_raw(list(launches), f0, self._raw.data_ptr())
+        for seg in segs:
+            if isinstance(seg, Kernels) and not done:
+                first = first_sweep_raw(list(seg.launches), f0, self._raw.data_ptr())
                 if first is not None:
-                    launches, done = first, True
-            out.append((kind, launches, lvl0))
+                    seg, done = Kernels(first, seg.lvl0), True
+            out.append(seg)
         return out
 
     def program(self, k):
@@ -820,12 +881,12 @@ class DDSolver:
             return [], s
         if k >= 2 and self.joinable():
             keys = [("head", s)]
-            pre = "b" if s == "a" else "a"
+            pre = _other(s)
             for _ in range(k - 1):
                 keys.append(("join", pre))
-                pre = "b" if pre == "a" else "a"
+                pre = _other(pre)
             keys.append(("tail", pre))
-            return keys, ("b" if pre == "a" else "a")
+            return keys, _other(pre)
         keys = []
         for _ in range(k):
             keys.append(("cycle", s))
@@ -838,35 +899,15 @@ class DDSolver:
 
     def run_kernels(self, key, i):
         """Kernel segment i of chunk `key` (graph-replayed after its first run)."""
-        segs, _ = self.chunk(key)
-        launches = segs[i][1]
-        gkey = (key, i)
-        stream = torch.cuda.current_stream(self.device)
+        launches = self.chunk(key)[0][i].launches
+
+        def issue():
+            _launch_list(launches, self.dtype, torch.cuda.current_stream(self.device))
         if len(launches) < self.graph_min:  # a graph launch costs more GPU time than a few eager launches
-            _launch_list(launches, self.dtype, stream)
-            return
-        if not self.use_graph or gkey not in self._graphs:
-            if self.use_graph:
-                self._graphs[gkey] = None  # eager once, capture on the second use
-            _launch_list(launches, self.dtype, stream)
-            return
-        g = self._graphs[gkey]
-        if g is None:
-            # thread-local capture: the communicator's own threads (the NCCL watchdog) keep running
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(stream)
-            try:
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    _launch_list(launches, self.dtype, s)
-            except RuntimeError:  # capture refused: this rank keeps launching eagerly
-                torch.cuda.synchronize(self.device)
-                self.use_graph = False
-                _launch_list(launches, self.dtype, stream)
-                return
-            stream.wait_stream(s)
-            self._graphs[gkey] = g
-        g.replay()
+            issue()
+        elif not self._graphs.run((key, i), issue, self.use_graph, confirm=_captured):
+            self.use_graph = False  # capture refused: this rank keeps launching eagerly
+            issue()
 
     # buffers the communication steps touch
     def level_rows(self, l, name, y0, y1):
@@ -918,7 +959,7 @@ class DDSolver:
 
     def gather(self, folded=False):
         """The level-Ld all-gather over the communicator (the coarse solver's f on every rank).  folded: the
-        staging copy and the placement run inside the kernel segments around it (_segs_of)."""
+        staging copy and the placement run inside the kernel segments around it (_fold_gather)."""
         if self.Pc == 1:
             self.comm.allgather(self.gather_target(), self.gather_source())
             return
@@ -1008,43 +1049,26 @@ class DDSolver:
                 while i + n < len(keys) and keys[i + n][0] == "join" and n < self.GRAPH_CYCLES:
                     n += 1
             block = keys[i:i + n]
-            gkey = ("cap",) + tuple(block)
-            g = self._graphs.get(gkey)
-            if g is None and gkey not in self._graphs:
-                self._graphs[gkey] = None  # eager once
-                self._run_chunks(block, captured=False)
-            elif g is None:
-                stream = torch.cuda.current_stream(self.device)
-                g = torch.cuda.CUDAGraph()
-                s = torch.cuda.Stream(self.device)
-                s.wait_stream(stream)
-                refused, error = False, None
-                try:
-                    with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                        self._run_chunks(block, captured=True)
-                except RuntimeError as e:
-                    if _is_capture_error(e):
-                        refused = True
-                    else:
-                        error = e
-                    g = None
-                    torch.cuda.synchronize(self.device)
-                stream.wait_stream(s)
-                n_refused, n_errors = self._agree(refused, error is not None)
+
+            def agreed(error):
+                """Between the capture and the first replay: did every rank capture?"""
+                refused = error is not None and _is_capture_error(error)
+                failed = error is not None and not refused
+                n_refused, n_errors = self._agree(refused, failed)
                 if n_errors:  # every rank raises: the failing one its own error, the others name it
-                    if error is not None:
+                    if failed:
                         raise error
                     raise RuntimeError(f"DDSolver: {n_errors} peer rank(s) failed inside a captured block of "
                                        f"cycles {block[0]}..{block[-1]} (rank {self.rank} aborts with them)")
-                if n_refused:  # some rank refused: every rank leaves the captured path
-                    self._capture_ok = False
-                    self._graphs = {k: v for k, v in self._graphs.items() if k[0] != "cap"}
-                    self._run_chunks(keys[i:], captured=False)
-                    return
-                self._graphs[gkey] = g
-                g.replay()
-            else:
-                g.replay()
+                return not n_refused
+
+            if not self._graphs.run(("cap",) + tuple(block),
+                                    lambda: self._run_chunks(block, captured=self._graphs.capturing), confirm=agreed):
+                # some rank refused: every rank leaves the captured path
+                self._capture_ok = False
+                self._graphs.discard(lambda k: k[0] == "cap")
+                self._run_chunks(keys[i:], captured=False)
+                return
             i += n
 
     def _agree(self, refused, failed):
@@ -1063,37 +1087,36 @@ class DDSolver:
         for key in keys:
             segs, _ = self.chunk(key)
             skip = -1
-            for i, (kind, st, lvl0) in enumerate(segs):
+            for i, seg in enumerate(segs):
                 if i == skip:
                     continue
-                if kind == "k":
-                    if lvl0 and pending is not None:
+                if isinstance(seg, Kernels):
+                    if seg.lvl0 and pending is not None:
                         self.comm.exchange_finish(pending)
                         pending = None
                     if self.split_join and self._split_join(segs, i):
                         skip = i + 1  # the exchange ran beside the interior join (eager launches off capture)
                     elif captured:
-                        _launch_list(segs[i][1], self.dtype, torch.cuda.current_stream(self.device))
+                        _launch_list(seg.launches, self.dtype, torch.cuda.current_stream(self.device))
                     else:
                         self.run_kernels(key, i)
-                elif st[0] == "exchanges":
+                elif isinstance(seg, Exchanges):
                     # coarse-level halos first (the next kernel needs them), the finest iterate's
                     # halo after, not waited for until a level-0 kernel runs: on RCCL both go out on
                     # the communicator's stream in this order, so the compute stream only waits for
                     # the first batch and level 1 .. Ld-1 run while the finest rows are in flight
-                    now, later = _split_exchanges(st[1], self.overlap_l0)
-                    packed = len(st) > 2 and st[2]
+                    now, later = _split_exchanges(seg.items, self.overlap_l0)
                     if pending is not None:
                         self.comm.exchange_finish(pending)
                         pending = None
                     if now:
-                        self.comm.exchange_many(self, now, packed=packed)
+                        self.comm.exchange_many(self, now, packed=seg.packed)
                     if later:
-                        pending = self.comm.exchange_many(self, later, wait=False, packed=packed)
-                elif st[0] == "gather":
-                    self.gather(folded=len(st) > 1 and st[1] is True)
-                elif st[0] == "scatter":
-                    self.scatter(st[1])
+                        pending = self.comm.exchange_many(self, later, wait=False, packed=seg.packed)
+                elif isinstance(seg, Gather):
+                    self.gather(folded=seg.folded)
+                else:
+                    self.scatter(seg.dst)
         if pending is not None:
             self.comm.exchange_finish(pending)
 
@@ -1128,8 +1151,8 @@ class DDSolver:
         exchange runs as [the segment's other kernels] -> the border rectangles' join, the pack, the exchange and
         the unpack on a side stream BESIDE the interior rectangle's join on the compute stream -> rejoin.  Returns
         False (nothing issued) where the pattern or the rectangles do not apply."""
-        launches = segs[i][1]
-        if i + 1 >= len(segs) or segs[i + 1][0] != "c" or segs[i + 1][1][0] != "exchanges" or self.P == 1:
+        launches = segs[i].launches
+        if i + 1 >= len(segs) or not isinstance(segs[i + 1], Exchanges) or self.P == 1:
             return False
         nj = [k for k, (name, _) in enumerate(launches) if name == "mg_cycle_join"]
         if len(nj) != 1 or any(name not in ("fn",) for name, _ in launches[nj[0] + 1:]):
@@ -1141,25 +1164,25 @@ class DDSolver:
         join = _params(launches[j])
         for p in ("norm_ws", "norm_hist", "norm_cnt"):  # the rectangles' join takes no norm
             del join[p]
-        rects = self.__dict__.setdefault("_rect_arrays", {})
+        rects = self._rect_arrays
         joins = []
         for key, rs in (("border", border), ("inner", [inner])):
             if key not in rects:
-                import ctypes
                 rects[key] = (ctypes.c_int * (4 * len(rs)))(*[x for r in rs for x in r])
-            joins.append(_lib.launch("mg_cycle_join_rects", **join, nrect=len(rs), rects=ctypes_addr(rects[key])))
+            joins.append(_lib.launch("mg_cycle_join_rects", **join, nrect=len(rs),
+                                     rects=ctypes.addressof(rects[key])))
         main = torch.cuda.current_stream(self.device)
-        side = self.__dict__.get("_side")
-        if side is None:
-            side = self._side = torch.cuda.Stream(self.device)
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        side = self._side
         _launch_list(launches[:j], self.dtype, main)
         side.wait_stream(main)
-        st = segs[i + 1][1]
+        exch = segs[i + 1]
         with torch.cuda.stream(side):
             _launch_list([joins[0]] + launches[j + 1:], self.dtype, side)
-            now, later = _split_exchanges(st[1], self.overlap_l0)
+            now, later = _split_exchanges(exch.items, self.overlap_l0)
             items = list(now) + list(later)
-            self.comm.exchange_many(self, items, packed=len(st) > 2 and st[2])
+            self.comm.exchange_many(self, items, packed=exch.packed)
         _launch_list([joins[1]], self.dtype, main)
         main.wait_stream(side)
         return True
@@ -1177,6 +1200,11 @@ _CAPTURE_WORDS = ("operation not permitted when stream is capturing", "stream is
                   "capture was invalidated", "capture sequence", "stream capture")
 
 
+def _captured(error):
+    """GraphCache confirm step of a kernel segment: keep the graph iff the capture raised nothing."""
+    return error is None
+
+
 def _is_capture_error(e):
     """Does this exception say that stream capture was refused (rather than that a call was wrong)?  HIP's
     stream-capture error codes 900-908 (hipErrorStreamCapture*, hipErrorCapturedEvent) by number or name, and the
@@ -1189,11 +1217,6 @@ def _is_capture_error(e):
         return True
     low = msg.lower()
     return any(w in low for w in _CAPTURE_WORDS)
-
-
-def ctypes_addr(arr):
-    import ctypes
-    return ctypes.addressof(arr)
 
 
 def _boundary_mask(H, W, like):
@@ -1214,7 +1237,6 @@ class _Staging:
     `records`: the block table (host int64 [nblocks, 4]); copy_blocks() launches any concatenation of them."""
 
     def __init__(self, views, device, dtype):
-        import numpy as np
         sizes = []
         for v in views:
             if v.dim() == 2:  # [B, run]: whole framed rows of a row slab
@@ -1240,7 +1262,6 @@ class _Staging:
 
 def copy_blocks(records, to_stage, esz, device, stream=None):
     """One fea_dd_copy_blocks launch (per 48 blocks) over a block table (host int64 [nblocks, 4])."""
-    import numpy as np
     recs = np.ascontiguousarray(records, dtype=np.int64)
     stream = torch.cuda.current_stream(device) if stream is None else stream
     _lib.call_raw("dd_copy_blocks", recs.ctypes.data, len(recs), esz, int(to_stage), stream.cuda_stream)
@@ -1317,12 +1338,10 @@ class TorchComm:
     def _cached_plan(self, s, items):
         # plans hold views of s's buffers: cached on s itself (keyed by this communicator), never on
         # the communicator under id(s), which a later solver could reuse
-        plans = s.__dict__.setdefault("_comm_plans", {})
         key = (id(self), tuple(items))
-        plan = plans.get(key)
+        plan = s._comm_plans.get(key)
         if plan is None:
-            plan = self._plan(s, items)
-            plans[key] = plan
+            plan = s._comm_plans[key] = self._plan(s, items)
         return plan
 
     def halo_pack(self, s, *item_lists):
@@ -1330,7 +1349,6 @@ class TorchComm:
         item_lists — ONE launch, f(stream) — or None when all regions go out in place.  The solver launches it
         inside its kernel segment (captured in the segment's graph) and then calls
         exchange_many(..., packed=True)."""
-        import numpy as np
         sends = [p["send"] for p in (self._cached_plan(s, items) for items in item_lists if items)
                  if p["ops"] and not p["direct"]]
         if not sends:
@@ -1414,15 +1432,14 @@ class LocalGroup:
         keys, end = r0.program(k)
         for key in keys:
             segs, _ = r0.chunk(key)
-            for i, (kind, st, _) in enumerate(segs):
-                if kind == "k":
+            for i, seg in enumerate(segs):
+                if isinstance(seg, Kernels):
                     for s in self.ranks:
-                        s.chunk(key)
                         s.run_kernels(key, i)
-                elif st[0] == "exchanges":
-                    for l, name, d in st[1]:
+                elif isinstance(seg, Exchanges):
+                    for l, name, d in seg.items:
                         self._exchange(l, name, d)
-                elif st[0] == "gather":
+                elif isinstance(seg, Gather):
                     chunks = [s.gather_source() for s in self.ranks]
                     for s in self.ranks:
                         tgt = s.gather_target()
@@ -1434,9 +1451,9 @@ class LocalGroup:
                             for r, ch in enumerate(chunks):
                                 tgt[r].copy_(ch)
                             s.gather_place(tgt)
-                elif st[0] == "scatter":
+                else:
                     for s in self.ranks:
-                        s.scatter(st[1])
+                        s.scatter(seg.dst)
         for s in self.ranks:
             s._state = end
             if k >= 1:

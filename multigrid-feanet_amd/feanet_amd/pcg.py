@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib, mesh_setup as ms, ops
-from .solver import MultigridSolver, _Level, run_segment
+from .graphs import GraphCache
+from .solver import MultigridSolver, _Level
 
 # scalar block layout and steps: include/feanet_hip.h (FEA_PCG_*)
 NSCALARS = 12
@@ -118,8 +119,7 @@ class PCGSolver:
         self.part = torch.zeros(self.B * self.per, dtype=torch.float64, device=self.device)
         self.sc = torch.zeros((self.B, NSCALARS), dtype=torch.float64, device=self.device)
         self.hist = torch.zeros((self.HIST_ROWS, self.B), dtype=torch.float64, device=self.device)
-        self._graphs = {}
-        self._eager_runs = {}
+        self._graphs = GraphCache(self.device)
         self._loaded = False
         self.flags = None        # after solve(): per-sample 1 converged, 2 breakdown, 0 still running
         self.iterations = None   # after solve(): per-sample iterations that moved x
@@ -255,13 +255,10 @@ class PCGSolver:
         return 6
 
     def _run_block(self, q, nb):
-        """nb iterations from parity q: eager, then captured, then replayed (solver.run_segment)."""
-        key = (q, nb, self.hist.data_ptr())
-        g = self._graphs.get(key)
-        if g is not None:  # captured: replay without rebuilding the launch list
-            g.replay()
-            return
-        run_segment(self, key, [rec for i in range(nb) for rec in self._iteration((q + i) % 2)])
+        """nb iterations from parity q: eager, then captured, then replayed (GraphCache)."""
+        self._graphs.run((q, nb, self.hist.data_ptr()),
+                         lambda: self._launch([rec for i in range(nb) for rec in self._iteration((q + i) % 2)]),
+                         self.use_graph)
 
     def iterate(self, k=1):
         """k iterations on the resident state (asynchronous; no host sync)."""
@@ -311,7 +308,6 @@ class PCGSolver:
         if max_iters + 1 > self.hist.shape[0]:
             self.hist = torch.zeros((max_iters + 1, self.B), dtype=torch.float64, device=self.device)
             self._graphs.clear()
-            self._eager_runs.clear()
         self.load(u0, eps=eps, rtol=rtol)
         it = 0
         while it < max_iters:

@@ -25,32 +25,13 @@ import numpy as np
 import torch
 
 from . import _lib, mesh_setup as ms, ops
-from .schedule import (OMDF, extend_tail, group_hmid, group_mid, hjac_schedule, pair_prolongations, pair_restrictions,
+from .graphs import GraphCache
+from .schedule import (OMDF, _other, extend_tail, group_hmid, group_mid, hjac_schedule, pair_prolongations, pair_restrictions,
                        vcycle_schedule)
 
 
 _SOLVERS = weakref.WeakValueDictionary()  # handle -> live MultigridSolver (torch.ops.feanet.mg_step)
 _HANDLES = itertools.count(1)
-
-
-def run_segment(s, key, launches):
-    """Run the launch list `launches` of solver s (its _launch, use_graph, _eager_runs, _graphs) under `key`: eager
-    the first time (lazy buffers and pointer arrays exist afterwards), captured as a HIP graph the second, replayed
-    after."""
-    if not s.use_graph or s._eager_runs.get(key, 0) == 0:
-        s._eager_runs[key] = s._eager_runs.get(key, 0) + 1
-        s._launch(launches)
-        return
-    g = s._graphs.get(key)
-    if g is None:
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(s.device)
-        side.wait_stream(torch.cuda.current_stream(s.device))
-        with torch.cuda.graph(g, stream=side):
-            s._launch(launches)
-        torch.cuda.current_stream(s.device).wait_stream(side)
-        s._graphs[key] = g
-    g.replay()
 
 
 def first_sweep_raw(launches, f0, raw):
@@ -345,8 +326,7 @@ class MultigridSolver:
         # and the third buffer c (a materialised end iterate) is packed with the same data as a/b
         self._ab_bc, self._ab_version = None, self._bc_version
         self._plans = {}
-        self._graphs = {}
-        self._eager_runs = {}
+        self._graphs = GraphCache(self.device)
         self.mass = ms.mass_stencil(size / n)
         self.handle = next(_HANDLES)  # torch.ops.feanet.mg_step(u, f, handle, cycles)
         _SOLVERS[self.handle] = self
@@ -481,7 +461,6 @@ class MultigridSolver:
                 self.w = (w[0], w[1])
                 self._plans.clear()
                 self._graphs.clear()
-                self._eager_runs.clear()
 
     # ------------------------------------------------------------------ schedule
     def _ptr(self, lvl, name):
@@ -726,7 +705,7 @@ class MultigridSolver:
         next cycle's SR(0); the new pre-smoothed iterate lands in the other buffer.  norm: also append the
         residual norm of the cycle's end iterate to the solve history (solve())."""
         L0, L1 = self.levels[0], self.levels[1]
-        out = out or ("b" if pre == "a" else "a")
+        out = out or _other(pre)
         if norm_ws is not None:
             norms = dict(norm_ws=norm_ws, norm_hist=None, norm_cnt=None)
         elif norm:
@@ -738,27 +717,27 @@ class MultigridSolver:
                            **self._prolongation(), **self._restriction(), **L0.geom_kw(), **self._coarse_pitch(0),
                            **norms)
 
-    def _run_segment(self, key, launches):
-        """Launch a fixed list of calls: eager the first time, then as a captured HIP graph (run_segment)."""
-        run_segment(self, key, launches)
+    def _run_graph(self, key, issue):
+        """issue()'s launches under `key`: eager the first time (lazy buffers and pointer arrays exist afterwards),
+        captured as a HIP graph the second, replayed after (GraphCache); always eager without use_graph."""
+        self._graphs.run(key, issue, self.use_graph)
 
     def joined_program(self, k):
         """vcycle(k) with joined cycle boundaries as [(segment key, launches)] plus the end buffer:
         the first cycle's SR(0), k-1 segments (coarse part + cycle join) and the last coarse part +
         PS(0).  (Also used by bench.py to time the join kernel inside the cycle.)"""
-        other = lambda b: "b" if b == "a" else "a"
         s0 = self._state
         plan, _ = self._plan(s0)
         head, mid = plan[0], plan[1:-1]
         ec_ptr = _lib.arg(plan[-1], "ec")  # level-1 correction the finest prolongation reads (same every cycle)
         prog = [(("head", s0), [head])]
-        pre = other(s0)
+        pre = _other(s0)
         for _ in range(k - 1):
             prog.append((("join", pre), mid + [self._join_call(pre, ec_ptr)]))
-            pre = other(pre)
-        tail = self._plan(other(pre))[0][-1]  # PS(0): pre -> other(pre)
+            pre = _other(pre)
+        tail = self._plan(_other(pre))[0][-1]  # PS(0): pre -> _other(pre)
         prog.append((("tail", pre), mid + [tail]))
-        return prog, other(pre)
+        return prog, _other(pre)
 
     GRAPH_CYCLES = 32  # max joined cycles per HIP graph
 
@@ -833,33 +812,29 @@ class MultigridSolver:
         pre-smooth (fea_mg_sweep_restrict).  The end iterate is materialised only when asked for
         (_iterate).  Replayed as few HIP graphs: blocks of GRAPH_CYCLES joins plus one block of the rest
         (pipe_blocks), keyed by (pipeline opened?, buffer, size)."""
-        other = lambda b: "b" if b == "a" else "a"
         plan, _ = self._plan("a")
         mid = plan[1:-1]  # levels >= 1 (they never touch the finest level's iterate buffers)
         ec_ptr = _lib.arg(plan[-1], "ec")  # level-1 correction the finest prolongation reads (same every cycle)
         if self._mid is None:
             s0 = self._state
             head = [self._plan(s0)[0][0]]
-            pre = other(s0)
+            pre = _other(s0)
         else:
             head, pre = [], self._mid["pre"]
         G = max(1, self.GRAPH_CYCLES)
         G = 1 << (G.bit_length() - 1)
         for nb in self.pipe_blocks(k, G):
-            key = ("pipe", bool(head), pre, nb)
-            g = self._graphs.get(key)
-            if g is not None:
-                g.replay()
-                if nb % 2:
-                    pre = other(pre)
-            else:
+            def issue(head=head, pre=pre, nb=nb):
                 launches = list(head)
                 for _ in range(nb):
                     launches += mid + [self._join_call(pre, ec_ptr)]
-                    pre = other(pre)
-                self._run_segment(key, launches)
+                    pre = _other(pre)
+                self._launch(launches)
+            self._run_graph(("pipe", bool(head), pre, nb), issue)
+            if nb % 2:
+                pre = _other(pre)
             head = []
-        self._mid = {"pre": pre, "last": other(pre), "mat": False}
+        self._mid = {"pre": pre, "last": _other(pre), "mat": False}
 
     def vcycle(self, k=1):
         """Run k V-cycles on the resident iterate (asynchronous; no host sync)."""
@@ -880,7 +855,7 @@ class MultigridSolver:
                 first = first_sweep_raw(plan, self.levels[0].f.data_ptr(), self._raw.data_ptr())
                 self._launch(plan if first is None else first)
             else:
-                self._run_segment(self._state, plan)
+                self._run_graph(self._state, lambda: self._launch(plan))
             self._state = end
 
     def step(self, u, f, cycles=1):
@@ -991,7 +966,7 @@ class MultigridSolver:
         head_launch = _lib.replace(head, norm_ws=self.ws.data_ptr(), norm_hist=self._hist.data_ptr(),
                                    norm_cnt=self._cnt.data_ptr())
         self._set_cnt(0)
-        S = "b" if s0 == "a" else "a"
+        S = _other(s0)
         # deferred norms: each joined cycle of a graph block writes its partial sums to its own set, one
         # reduction launch per graph block appends the block's rows
         per = _lib.join_norm_parts(self.B, L0.H, L0.W, L0.esz)
@@ -1017,22 +992,20 @@ class MultigridSolver:
             p, t, last = S, X, None
             for blk in ([nb] if nb <= Gmax else self.graph_blocks(nb, Gmax)):
                 # (first read, first write, second write) fixes the whole buffer sequence of the block
-                key = ("sblock", with_head, p, t, Y if t == X else X, blk, gen)
-                g = self._graphs.get(key)
-                if g is not None:  # captured: replay without rebuilding the launch list
-                    for _ in range(blk):
-                        last, p, t = p, t, (Y if t == X else X)
-                    g.replay()
-                    with_head = False
-                    continue
-                launches = [head_launch] if with_head else []
+                def issue(with_head=with_head, p=p, t=t, blk=blk):
+                    launches = [head_launch] if with_head else []
+                    for i in range(blk):  # cycle i of the graph block: partial sums into set i
+                        launches += mid + [self._join_call(p, ec_ptr, out=t,
+                                                           norm_ws=self._sws.data_ptr() + 8 * i * stride)]
+                        p, t = t, (Y if t == X else X)
+                    launches.append(_lib.launch("norm_append", ws=self._sws.data_ptr(), stride=stride, per=per,
+                                                B=self.B, nrows=blk, hist=self._hist.data_ptr(),
+                                                cnt=self._cnt.data_ptr()))
+                    self._launch(launches)
+                self._run_graph(("sblock", with_head, p, t, Y if t == X else X, blk, gen), issue)
                 with_head = False
-                for i in range(blk):  # cycle i of the graph block: partial sums into set i
-                    launches += mid + [self._join_call(p, ec_ptr, out=t, norm_ws=self._sws.data_ptr() + 8 * i * stride)]
+                for _ in range(blk):
                     last, p, t = p, t, (Y if t == X else X)
-                launches.append(_lib.launch("norm_append", ws=self._sws.data_ptr(), stride=stride, per=per, B=self.B,
-                                            nrows=blk, hist=self._hist.data_ptr(), cnt=self._cnt.data_ptr()))
-                self._run_segment(key, launches)
             return last, p
 
         hist = None
@@ -1090,8 +1063,8 @@ class MultigridSolver:
                 q = min(q + max(0.0, rs[1] - rs[0]), 1.15 * q)
         # v of the last cycle: PS(0) from the last join's inputs (its pre-smoothed iterate `last_read`, the
         # level-1 correction untouched since), into a ping-pong buffer of the unjoined plans
-        D = "b" if last_read == "a" else "a"
-        self._run_segment(("tail", last_read, D), [self._post_smooth(last_read, D)])
+        D = _other(last_read)
+        self._run_graph(("tail", last_read, D), lambda: self._launch([self._post_smooth(last_read, D)]))
         self._state = D
         mark("tail")
         u = self.solution()

@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "multigrid-feanet_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from feanet_amd.dd import DDSolver, LocalGroup  # noqa: E402
+from feanet_amd.dd import DDSolver, Kernels, LocalGroup  # noqa: E402
 from feanet_amd.pcg import PCGSolver  # noqa: E402
 from feanet_amd.solver import MultigridSolver  # noqa: E402
 from tools.dd_projection import PackComm  # noqa: E402
@@ -135,8 +135,8 @@ def main():
             d.load()
             d.vcycle(3)
             torch.cuda.synchronize()
-            names = [r[0] for key in (("head", "a"), ("cycle", "a")) for kind, st, _ in d.chunk(key)[0] if kind == "k"
-                     for r in st]
+            names = [r[0] for key in (("head", "a"), ("cycle", "a")) for seg in d.chunk(key)[0]
+                     if isinstance(seg, Kernels) for r in seg.launches]
             sends = sorted({x for x in names if x.endswith("_send")})
             L0 = d.local.levels[0]
             emit(f"dd rank {rank} of {grid[0]} x {grid[1]} {n + 1}^2 Ld={Ld} {'+'.join(sends) or 'no _send'}", "vcycle3",

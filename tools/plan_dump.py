@@ -2,7 +2,8 @@
 layer leaves every launch, its order and every argument as they were.
 
 For a set of small solver configurations (every kernel name MultigridSolver._plan_bytes accounts for, the joined
-program, the PCG iteration, the decomposed solver's folded gather, in-place coarse read and first HJac chunk) prints
+program, the PCG iteration, the decomposed solver's folded gather, in-place coarse read, first HJac chunk and the
+segment builder's switches: overlap_l0, fold_gather=False, one rank, split_join) prints
 each launch record as  name(arg, arg, ...)  in C-ABI order — a pointer as <level>.<buffer>, a table's name, a
 PtrArray element by element, otherwise base+offset — and the integer bytes_per_vcycle().  The text holds no
 address, so two checkouts that bind the same plans print the same bytes:
@@ -20,7 +21,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from feanet_amd import mesh_setup as ms  # noqa: E402
-from feanet_amd.dd import DDSolver  # noqa: E402
+from feanet_amd.dd import DDSolver, Exchanges, Gather, Kernels  # noqa: E402
 from feanet_amd.pcg import PCGSolver  # noqa: E402
 from feanet_amd.solver import MultigridSolver  # noqa: E402
 from tools.dd_projection import PackComm  # noqa: E402
@@ -163,6 +164,16 @@ def dump_pcg(label, p):
     emit()
 
 
+def comm_text(seg):
+    """A communication step in the wording the plan text has always had: the step's name, then its fields, a
+    flag only where it is set."""
+    if isinstance(seg, Exchanges):
+        return repr(("exchanges", seg.items) + ((True,) if seg.packed else ()))
+    if isinstance(seg, Gather):
+        return repr(("gather",) + ((True,) if seg.folded else ()))
+    return repr(("scatter", seg.dst))
+
+
 def dump_dd(label, d, keys):
     emit(f"== {label}")
     emit(f"exchange depths {d.depths}, coarse plan -> {d.coarse_end}")
@@ -171,12 +182,12 @@ def dump_dd(label, d, keys):
         names = Names()
         names.add_dd(d)
         emit(f"chunk {key} -> {end}")
-        for kind, st, lvl0 in segs:
-            if kind == "k":
-                emit(f" kernels (level 0: {lvl0})")
-                dump_launches(names, st, "   ")
+        for seg in segs:
+            if isinstance(seg, Kernels):
+                emit(f" kernels (level 0: {seg.lvl0})")
+                dump_launches(names, seg.launches, "   ")
             else:
-                emit(f" comm {st!r}")
+                emit(f" comm {comm_text(seg)}")
     emit()
 
 
@@ -247,6 +258,14 @@ def main():
     # learned smoother: the first chunk after load() (the un-reset iterate)
     dd("dd hjac 512^2 4 ranks (2, 2) rank 0 Ld=2", keys=[("first", "a"), ("cycle", "b")], load=True, n=512, rows=512,
        rank=0, world=4, agglomerate=2, grid=(2, 2), smoother="hjac", hnet=hnet())
+
+    # the segment builder's switches: the finest halo as a batch of its own, the agglomeration's copies unfolded,
+    # one rank (no exchange, the all-gather a device copy), and split_join (which chunk() must not depend on)
+    for label, kw in (("overlap_l0", dict(world=4, grid=(2, 2), overlap_l0=True)),
+                      ("fold_gather=False", dict(world=4, grid=(2, 2), fold_gather=False)),
+                      ("one rank", dict(world=1)),
+                      ("split_join", dict(world=4, grid=(2, 2), split_join=True))):
+        dd(f"dd 512^2 Ld=2 rank 0, {label}", n=512, rows=512, rank=0, agglomerate=2, **kw)
 
     text = "\n".join(OUT) + "\n"
     if len(sys.argv) > 1:
