@@ -222,6 +222,16 @@ size_t fea_transfer_weight_grad_ws_bytes_f64(int C, int B, int Hc, int Wc);
  *     Norm workspaces: a call with norm_ws / ws writes nowhere but inside fea_norm_workspace_bytes(B, H, W) of it;
  *     the deferred cycle join writes exactly B * fea_mg_join_norm_parts doubles.  An appended norm writes row cnt[1]
  *     of the history (B doubles) and cnt[1], nothing else.
+ *
+ *     Batches.  The B samples of a call are independent problems that share tables and pattern maps.  The launch
+ *     geometry (rows per wave task, streaming stores) follows B and the shape, the results do not: sample b's field
+ *     outputs and send blocks are the same bits in every batch that holds it, alone included; its norms are sums of
+ *     the same squares in double, equal to within the order of summation (bitwise for equal partial counts).
+ *     Samples are isolated: no output, norm or partial sum of sample b depends on any other sample's data, so a
+ *     sample that has diverged to Inf / NaN leaves its neighbours' bits alone; and a non-finite node of the iterate
+ *     makes every residual norm of ITS sample non-finite (never a finite value that could pass a convergence test).
+ *     The same holds for the Krylov operations of section 3, whose partial sums are bitwise independent of B.
+ *     (tests/test_gpu_task_heights.py pins both at every task height.)
  * ------------------------------------------------------------------------- */
 
 /* contiguous [B,1,H,W] -> framed, applying u*geo + bc (src NULL: u = 0; geo NULL: the square geometry,

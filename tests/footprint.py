@@ -20,7 +20,10 @@ An in-place operand (x and r of fea_pcg_update) counts as an output whose "canar
 A `loose` write set (a norm workspace the header only bounds) may be written anywhere inside: there an element is
 either untouched in both runs or bit-identical.
 
-Nothing here needs an oracle: tables are random with a positive diagonal, pattern maps random ids."""
+Nothing here needs an oracle: tables are random with a positive diagonal, pattern maps random ids.
+
+The same descriptors drive the task-height ladders and the sample-isolation runs of test_gpu_task_heights.py (the
+section "task-height ladders" at the end): there the buffers stay on the GPU and only run Z is used."""
 import ctypes
 
 import numpy as np
@@ -51,7 +54,8 @@ NSCAL, BETA, ALPHA, RNORM, DONE = 12, 4, 3, 5, 6    # FEA_PCG_* of include/feane
 
 class FootprintError(AssertionError):
     """kind: the assertion that failed, 'a' .. 'd' (module docstring); 'v': an exact expected value (the halo copies,
-    fea_mg_unpack, the zeros fea_pcg_residual stores on the boundary nodes)."""
+    fea_mg_unpack, the zeros fea_pcg_residual stores on the boundary nodes); 'h', 's', 'n': the ladder's assertions
+    (height or batch dependence, a leak between samples, a NaN dropped from a norm; see "task-height ladders")."""
 
     def __init__(self, kind, operand, msg):
         super().__init__(f"({kind}) {operand}: {msg}")
@@ -68,7 +72,7 @@ class Geo:
             ld, bs = _lib.mg_layout(H, W, esz)
         if pid:
             B, bs = 1, (H + 2) * ld
-        self.H, self.W, self.B, self.esz, self.ld, self.bs = H, W, B, esz, ld, bs
+        self.H, self.W, self.B, self.esz, self.ld, self.bs, self.is_pid = H, W, B, esz, ld, bs, pid
         self.off = 128 // esz - 1
         self.numel = B * bs + SLACK
 
@@ -120,12 +124,41 @@ def canary(n, dtype, byte):
 
 
 class Operand:
-    """name; role 'in' / 'out' / 'inout'; z, p: the raw buffer before run Z / run P; mask: the write set."""
+    """name; role 'in' / 'out' / 'inout'; z, p: the raw buffer before run Z / run P; mask: the write set.
 
-    def __init__(self, name, role, z, p, mask=None, loose=False, geo=None):
-        self.name, self.role, self.z, self.p, self.mask, self.loose, self.geo = name, role, z, p, mask, loose, geo
-        assert z.shape == p.shape and z.dtype == p.dtype and z.ndim == 1
-        assert (role == "in") == (mask is None) and (mask is None or mask.shape == z.shape)
+    make: builds (z, p) on first use instead (the tall ladder cases never need p, and build z on the device from
+    `nodes`, the compact [B, H, W] node values of a framed field, or `fill`, an output's canary byte).
+    sample(B, b): where sample b lives in the raw buffer of a call with B samples (a slice or an index array); None:
+    the operand is shared by all samples (tables, pattern maps, counters, loosely bounded workspaces).
+    norm: 'norm' a per-sample norm (one double per sample), 'parts' a per-sample set of partial sums, 'ws' the loosely
+    bounded workspace behind a norm (only the number of slots stored to is read from it)."""
+
+    def __init__(self, name, role, z=None, p=None, mask=None, loose=False, geo=None, make=None, nodes=None,
+                 fill=None, dtype=None, numel=None, sample=None, norm=None):
+        self.name, self.role, self.mask, self.loose, self.geo = name, role, mask, loose, geo
+        self._z, self._p, self._make, self.nodes, self.fill = z, p, make, nodes, fill
+        self.dtype = np.dtype(z.dtype if z is not None else dtype)
+        self.numel = z.size if z is not None else numel
+        self.sample, self.norm = sample, norm
+        if sample is None and geo is not None and not geo.is_pid:
+            self.sample = lambda B, b, bs=geo.bs: slice(b * bs, (b + 1) * bs)
+        if z is not None:
+            assert z.shape == p.shape and z.dtype == p.dtype and z.ndim == 1
+        assert (role == "in") == (mask is None) and (mask is None or mask.shape == (self.numel,))
+
+    def _built(self):
+        if self._z is None:
+            self._z, self._p = self._make()
+            assert self._z.shape == self._p.shape == (self.numel,) and self._z.dtype == self._p.dtype == self.dtype
+        return self._z, self._p
+
+    @property
+    def z(self):
+        return self._built()[0]
+
+    @property
+    def p(self):
+        return self._built()[1]
 
     def where(self, i):
         return self.geo.where(i) if self.geo is not None else f"element {int(i)}"
@@ -135,16 +168,21 @@ def field_in(name, geo, dtype, nodes, keep=None, finite=False):
     """an input field; keep: mask of non-node storage whose (zero) content the header requires; finite: the header
     requires finite values in the frame (the B * bstride elements), so the poison there is finite garbage and only
     the slack behind the last sample is NaN"""
-    z, p = geo.framed(nodes, 0, dtype), geo.framed(nodes, np.nan, dtype)
-    if finite:
-        p[~geo.nodes() & (np.arange(geo.numel) < geo.B * geo.bs)] = FINITE
-    if keep is not None:
-        p[keep] = z[keep]
-    return Operand(name, "in", z, p, geo=geo)
+    nodes = np.asarray(nodes, dtype)
+
+    def make():
+        z, p = geo.framed(nodes, 0, dtype), geo.framed(nodes, np.nan, dtype)
+        if finite:
+            p[~geo.nodes() & (np.arange(geo.numel) < geo.B * geo.bs)] = FINITE
+        if keep is not None:
+            p[keep] = z[keep]
+        return z, p
+    return Operand(name, "in", make=make, geo=geo, nodes=nodes, dtype=dtype, numel=geo.numel)
 
 
 def field_out(name, geo, dtype, mask):
-    return Operand(name, "out", canary(geo.numel, dtype, C1), canary(geo.numel, dtype, C2), mask, geo=geo)
+    return Operand(name, "out", make=lambda: (canary(geo.numel, dtype, C1), canary(geo.numel, dtype, C2)), mask=mask,
+                   geo=geo, fill=C1, dtype=dtype, numel=geo.numel)
 
 
 def field_inout(name, geo, dtype, nodes, mask, keep=None):
@@ -155,25 +193,35 @@ def field_inout(name, geo, dtype, nodes, mask, keep=None):
 
 def pid_in(name, geo, ids, ntab, rng):
     """a framed pattern map: poison is random VALID ids (an id >= ntab would index past the tables)"""
-    z = geo.framed(ids, 0, np.uint8)
-    p = rng.integers(0, ntab, geo.numel).astype(np.uint8)
-    p[geo.nodes()] = z[geo.nodes()]
-    return Operand(name, "in", z, p, geo=geo)
+    ids = np.asarray(ids, np.uint8)
+    seed = int(rng.integers(1 << 30))       # (drawn now: the case's other operands do not depend on when p is built)
+
+    def make():
+        z = geo.framed(ids, 0, np.uint8)
+        p = np.random.default_rng(seed).integers(0, ntab, geo.numel).astype(np.uint8)
+        p[geo.nodes()] = z[geo.nodes()]
+        return z, p
+    return Operand(name, "in", make=make, geo=geo, nodes=ids[None], dtype=np.uint8, numel=geo.numel)
 
 
-def flat_in(name, arr):
+def flat_in(name, arr, sample=None):
     a = np.ascontiguousarray(arr).reshape(-1)
-    return Operand(name, "in", a, a.copy())
+    return Operand(name, "in", a, a.copy(), sample=sample)
 
 
-def flat_out(name, n, dtype, mask=None, loose=False):
+def flat_out(name, n, dtype, mask=None, loose=False, sample=None, norm=None):
     return Operand(name, "out", canary(n, dtype, C1), canary(n, dtype, C2),
-                   np.ones(n, bool) if mask is None else mask, loose)
+                   np.ones(n, bool) if mask is None else mask, loose, sample=sample, norm=norm)
 
 
 def flat_inout(name, arr, mask):
     a = np.ascontiguousarray(arr).reshape(-1)
     return Operand(name, "inout", a, a.copy(), mask)
+
+
+def rows(per):
+    """sample(B, b) of a flat [B, per] operand"""
+    return lambda B, b: slice(b * per, (b + 1) * per)
 
 
 # ----------------------------------------------------------------------------- the four assertions
@@ -239,6 +287,7 @@ class Case:
     def __init__(self, entry, suf, label):
         self.entry, self.suf, self.label = entry, suf, label
         self.ops, self.calls, self.expect = [], [], {}
+        self.B = self.norm_n = self.nan_op = None     # samples; nodes a norm of the call sums; the field it is a norm of
 
     def __repr__(self):
         return f"{self.entry}[{self.suf} {self.label}]"
@@ -267,9 +316,17 @@ def run_case(case, launch):
 def gpu_launch(case, bufs):
     """Upload, issue the case's calls on the default stream, download."""
     import torch
-    from feanet_amd import _lib
     dev = {n: torch.from_numpy(a.view(np.uint8)).cuda() for n, a in bufs.items()}
-    addr = {n: t.data_ptr() for n, t in dev.items()}
+    keep = _issue(case, {n: t.data_ptr() for n, t in dev.items()})
+    torch.cuda.synchronize()
+    del keep
+    return {n: dev[n].cpu().numpy().view(bufs[n].dtype) for n in bufs}
+
+
+def _issue(case, addr):
+    """the case's calls on the default stream, on buffers at the device addresses addr -> the host arrays the calls
+    were given (alive until the caller has synchronised)"""
+    from feanet_amd import _lib
     keep = []
 
     def conv(x):
@@ -287,8 +344,7 @@ def gpu_launch(case, bufs):
     for sym, args in case.calls:
         rc = getattr(_lib.lib(), sym)(*[conv(a) for a in args], None)
         assert rc == 0, f"{case}: {sym} returned {rc}"
-    torch.cuda.synchronize()
-    return {n: dev[n].cpu().numpy().view(bufs[n].dtype) for n in bufs}
+    return keep
 
 
 # ----------------------------------------------------------------------------- case builder
@@ -314,6 +370,7 @@ class Builder:
         self.a.update(B=B, H=H, W=W, w0=W0, w1=W1)
         self.ntab = MAXP if two else 1
         self.geos = [Geo(H, W, B, self.esz)]
+        self.case.B, self.case.norm_n = B, (H - 2) * (W - 2)
         while self.geos[-1].H >= 5 and self.geos[-1].W >= 5 and self.geos[-1].H & 1 and self.geos[-1].W & 1:
             self.geos.append(self.geos[-1].coarse())
 
@@ -358,11 +415,11 @@ class Builder:
             self.a[arg] = ref
         return ref
 
-    def flat_in(self, arg, arr):
-        self.a[arg] = self.case.add(flat_in(arg, arr))
+    def flat_in(self, arg, arr, sample=None):
+        self.a[arg] = self.case.add(flat_in(arg, arr, sample))
 
-    def flat_out(self, arg, n, dtype, mask=None, loose=False):
-        self.a[arg] = self.case.add(flat_out(arg, n, dtype, mask, loose))
+    def flat_out(self, arg, n, dtype, mask=None, loose=False, sample=None, norm=None):
+        self.a[arg] = self.case.add(flat_out(arg, n, dtype, mask, loose, sample, norm))
 
     def tables(self):
         """random coefficient tables with a positive diagonal, and omega / d"""
@@ -379,14 +436,15 @@ class Builder:
         """the per-wave partial sums of a Krylov kernel: exactly B * fea_pcg_parts doubles"""
         from feanet_amd import _lib
         g = self.geos[0]
-        n = g.B * int(_lib.lib().fea_pcg_parts(g.H, g.W, self.esz))
-        self.flat_out("part", n + 16, np.float64, np.arange(n + 16) < n)
+        per = int(_lib.lib().fea_pcg_parts(g.H, g.W, self.esz))
+        n = g.B * per
+        self.flat_out("part", n + 16, np.float64, np.arange(n + 16) < n, sample=rows(per), norm="parts")
 
     def scalars(self, done=0.0):
         s = np.zeros((self.geos[0].B, NSCAL))
         s[:, BETA], s[:, ALPHA], s[:, DONE] = 0.37, 0.61, done
         s[:, RNORM] = 3.0 * 2.0 ** (5 * np.arange(self.geos[0].B))
-        self.flat_in("scalars", s)
+        self.flat_in("scalars", s, rows(NSCAL))
 
     def norm(self, kind):
         """norm operands of cycle_join / sweep_restrict: '' none, 'hist' appended in the call, 'defer' partials only"""
@@ -399,11 +457,14 @@ class Builder:
         nws = _lib.norm_workspace_bytes(g.B, g.H, g.W) // 8
         per = _lib.join_norm_parts(g.B, g.H, g.W, self.esz)
         if kind == "defer":
-            self.flat_out("norm_ws", nws + 16, np.float64, np.arange(nws + 16) < g.B * per)
+            self.flat_out("norm_ws", nws + 16, np.float64, np.arange(nws + 16) < g.B * per, sample=rows(per),
+                          norm="parts")
         else:
-            self.flat_out("norm_ws", nws + 16, np.float64, np.arange(nws + 16) < nws, loose=True)
+            self.flat_out("norm_ws", nws + 16, np.float64, np.arange(nws + 16) < nws, loose=True, norm="ws")
         row = np.arange(4 * g.B) // g.B == 1          # history row cnt[1] = 1
-        hist = self.case.add(flat_out("norm_hist", 4 * g.B, np.float64, row))
+        hist = self.case.add(flat_out("norm_hist", 4 * g.B, np.float64, row,
+                                      sample=lambda B, b: slice(B + b, B + b + 1), norm="norm"))
+        self.case.nan_op = "u"
         cnt = self.case.add(flat_inout("norm_cnt", np.array([7, 1], np.uint32), np.array([False, True])))
         self.set(norm_hist=None if kind == "defer" else hist, norm_cnt=None if kind == "defer" else cnt)
         self.call()
@@ -425,8 +486,8 @@ class Builder:
 # ----------------------------------------------------------------------------- one builder per entry point
 def _pack(b):
     g = b.geos[0]
-    b.flat_in("src", b.rand(g))
-    b.flat_in("bc", b.rand(g))
+    b.flat_in("src", b.rand(g), rows(g.H * g.W))
+    b.flat_in("bc", b.rand(g), rows(g.H * g.W))
     b.set(geo=None, geo_bs=0, bc_bs=g.H * g.W)
     b.fout("dst", mask=g.nodes())
 
@@ -435,7 +496,7 @@ def _unpack(b):
     g = b.geos[0]
     nodes = b.rand(g)
     b.a["src"] = b.case.add(field_in("src", g, b.dt, nodes))
-    b.flat_out("dst", g.B * g.H * g.W, b.dt)
+    b.flat_out("dst", g.B * g.H * g.W, b.dt, sample=rows(g.H * g.W))
     b.case.expect["dst"] = (np.ones(nodes.size, bool), nodes.ravel())
 
 
@@ -459,7 +520,8 @@ def _send(b, lev):
     own = np.zeros((g.B, r1 - r0, c1 - c0), bool)
     own[:, 1 - r0:g.H - 1 - r0, :g.W - 1 - c0] = True
     b.set(r0=r0, r1=r1, c0=c0, c1=c1)
-    b.flat_out("send", own.size + 8, b.dt, np.concatenate([own.ravel(), np.zeros(8, bool)]))
+    b.flat_out("send", own.size + 8, b.dt, np.concatenate([own.ravel(), np.zeros(8, bool)]),
+               sample=rows((r1 - r0) * (c1 - c0)))
 
 
 def _zero_restrict_send(b):
@@ -495,10 +557,12 @@ def _residual_norm(b):
     g = b.geos[0]
     b.fin("u"), b.fin("f"), b.pid("pid")
     nws = _lib.norm_workspace_bytes(g.B, g.H, g.W) // 8
-    b.flat_out("ws", nws + 16, np.float64, np.arange(nws + 16) < nws, loose=True)
-    b.flat_out("out", g.B + 4, np.float64, np.arange(g.B + 4) < g.B)
+    b.flat_out("ws", nws + 16, np.float64, np.arange(nws + 16) < nws, loose=True, norm="ws")
+    b.flat_out("out", g.B + 4, np.float64, np.arange(g.B + 4) < g.B, sample=rows(1), norm="norm")
+    b.case.nan_op = "u"
     if b.mode == "range":
         b.set(rlo=1, rhi=max(2, g.H // 2), clo=max(1, g.W // 3), chi=g.W - 1)
+        b.case.norm_n = (b.a["rhi"] - 1) * (g.W - 1 - b.a["clo"])
 
 
 def _cycle_join(b):
@@ -579,7 +643,9 @@ def _mid(b):
         g = b.geos[0]
         Pr = Pc = 2
         b.set(Pr=Pr, Pc=Pc, gcr=(g.H - 1) // Pr, gcc=(g.W - 1) // Pc)
-        b.flat_in("gsrc", b.rng.standard_normal(Pr * Pc * g.B * b.a["gcr"] * b.a["gcc"]).astype(b.dt))
+        blk = b.a["gcr"] * b.a["gcc"]             # [Pr * Pc][B][gcr][gcc]
+        b.flat_in("gsrc", b.rng.standard_normal(Pr * Pc * g.B * blk).astype(b.dt),
+                  lambda B, i: ((np.arange(Pr * Pc)[:, None] * B + i) * blk + np.arange(blk)[None, :]).ravel())
 
 
 def _hmid(b):
@@ -599,6 +665,7 @@ def _hmid(b):
 def _pcg_residual(b):
     g = b.geos[0]
     b.fin("x"), b.fin("f"), b.fout("r", mask=g.nodes()), b.pid("pid"), b.part()
+    b.case.nan_op = "x"
     b.case.expect["r"] = (g.boundary(), np.zeros(g.numel, b.dt))      # zeros on the boundary nodes
 
 
@@ -609,6 +676,7 @@ def _pcg_direction(b):
     else:
         b.fin("z", krylov=True)
     b.fin("p_in", krylov=True), b.fout("p_out"), b.pid("pid"), b.scalars(), b.part()
+    b.case.nan_op = "z32" if b.has("z32") else "z"
 
 
 def _pcg_update(b):
@@ -621,12 +689,14 @@ def _pcg_update(b):
     if b.has("r32"):
         g32 = Geo(g.H, g.W, g.B, 4)
         b.fout("r32", geo=g32, dt=np.float32, mask=np.zeros(g32.numel, bool) if frozen else None)
-        b.flat_in("sb", np.full(g.B, 0.5))
+        b.flat_in("sb", np.full(g.B, 0.5), rows(1))
+    b.case.nan_op = "r"           # (a frozen sample sums its r again, whatever p holds)
 
 
 def _pcg_dot(b):
     g = b.geos[0]
     b.fin("r", krylov=True), b.part()
+    b.case.nan_op = "r"
     if b.has("z32"):
         b.fin("z32", krylov=True, geo=Geo(g.H, g.W, g.B, 4), dt=np.float32)
     else:
@@ -637,7 +707,7 @@ def _pcg_narrow(b):
     g = b.geos[0]
     b.fin("r", krylov=True), b.scalars()
     b.fout("r32", geo=Geo(g.H, g.W, g.B, 4), dt=np.float32)
-    b.flat_out("sb", g.B + 4, np.float64, np.arange(g.B + 4) < g.B)
+    b.flat_out("sb", g.B + 4, np.float64, np.arange(g.B + 4) < g.B, sample=rows(1))
 
 
 # ----------------------------------------------------------------------------- halo pack / rectangle copies
@@ -791,3 +861,327 @@ def build_case(entry, suf, shape, two, mode):
 
 def cases(entry, suf):
     return [build_case(entry, suf, shape, two, mode) for shape, two, mode in DESC[entry].params()]
+
+
+# ----------------------------------------------------------------------------- task-height ladders
+# A framed or Krylov launch splits a level into wave tasks of rb rows; the host picks rb from the batch size and the
+# shape (pick_rb, balanced_rb, join_config of csrc/), and the results are documented to be the same bits whatever it
+# picks.  A ladder runs one call at batch sizes that reach every height: the case is built once for the top rung, every
+# lower rung is a prefix of its samples (and one rung holds the last sample alone), and sample b's outputs must be the
+# same bytes in every rung that contains it.  Three more error kinds:
+#   'h'  a sample's output differs between two rungs (the result depends on the task height or on the batch);
+#   's'  an output of another sample changed when every node of sample j became NaN (a leak between samples);
+#   'n'  a norm of a sample with a NaN node is finite (a diverged sample would pass as converged).
+# Everything below works on numpy arrays (the host tests' stand-in kernels) and on torch tensors that stay on the GPU.
+K_TARGET_WAVES, K_RB = 2048, 32       # kTargetWaves, kRB of csrc/framed_strip.h
+LADDER_H, LADDER_W, LADDER_W2 = 4097, 33, 163
+BATCH_RUNGS = (1, 2, 4, 8, 16)        # at H = 4097, one strip: rb = 2, 4, 8, 16, 32
+CAP64 = ("mg_sweep_restrict", "mg_cycle_join")      # their cap is 64 rows: one more rung, B = 32
+SMALL_RUNGS = (1, 2, 3)               # entry points whose geometry ignores B, at their DESC shapes
+BATCH_FREE = ("mg_pack", "mg_unpack", "mg_coarse_tail", "mg_coarse_tail_ext", "mg_hjac_tail", "mg_mid_down",
+              "mg_mid_down_gathered", "mg_mid_up", "mg_hmid_down", "mg_hmid_up")
+U_DOUBLE = 2.0 ** -53                 # every norm and partial sum accumulates in double (wave_sum, k_norm_final)
+
+
+def pick_rb(B, nstrips, rows, maxrb=K_RB):
+    """restatement of pick_rb (csrc/framed_strip.h): the coverage guard's, not an oracle for values"""
+    rb = maxrb
+    while rb > 2 and B * nstrips * -(-rows // rb) < K_TARGET_WAVES:
+        rb //= 2
+    return rb
+
+
+def nstrips(W, esz):
+    return -(-(W - 2) // (64 * (16 // esz)))
+
+
+def ladder_w2(entry):
+    """the two-strip width: 163, or 161 where two coarser levels need (W + 1) / 2 odd as well"""
+    return 161 if entry in ("mg_zero_restrict2", "mg_zero_restrict2_send", "mg_prolong2") else LADDER_W2
+
+
+def rungs_of(entry):
+    if entry in BATCH_FREE:
+        return SMALL_RUNGS
+    return BATCH_RUNGS + (32,) if entry in CAP64 else BATCH_RUNGS
+
+
+def ladder_heights(entry, esz, W=LADDER_W, rungs=None):
+    """the nominal (power-of-two) task height of every rung; raises when the ladder no longer reaches five distinct
+    heights (six for the cap-64 kernels)"""
+    cap = 2 * K_RB if entry in CAP64 else K_RB
+    if entry.startswith(("pcg_", "fea_pcg_")):      # pcg_geom: the height of ONE sample, whatever the batch
+        return [pick_rb(1, nstrips(W, esz), LADDER_H - 2)] * len(rungs or rungs_of(entry))
+    hs = [pick_rb(B, nstrips(W, esz), LADDER_H - 2, cap) for B in (rungs or rungs_of(entry))]
+    if rungs is None and len(set(hs)) != (6 if entry in CAP64 else 5):
+        raise AssertionError(f"{entry}: the batch ladder reaches heights {hs}: kTargetWaves or kRB changed, re-pick "
+                             "the ladder")
+    return hs
+
+
+def _is_np(a):
+    return isinstance(a, np.ndarray)
+
+
+def _bits(a):
+    """the same bytes as integers: == on them is a bitwise comparison (NaNs and signed zeros included)"""
+    if _is_np(a):
+        return a.view(f"u{a.dtype.itemsize}")
+    import torch
+    return a.view({1: torch.uint8, 4: torch.int32, 8: torch.int64}[a.element_size()])
+
+
+def _ix(a, idx):
+    if isinstance(idx, slice) or _is_np(a):
+        return idx
+    import torch
+    return torch.as_tensor(np.asarray(idx), device=a.device)
+
+
+def _first(bad):
+    return int(np.flatnonzero(bad)[0]) if _is_np(bad) else int(bad.nonzero()[0, 0])
+
+
+def _f64(a):
+    if _is_np(a):
+        return a.view(np.float64)
+    import torch
+    return a.view(torch.float64)
+
+
+def _mask(op, like):
+    """the operand's write set next to `like` (uploaded once per operand)"""
+    if _is_np(like):
+        return op.mask
+    if getattr(op, "_dmask", None) is None:
+        import torch
+        op._dmask = torch.from_numpy(op.mask).to(like.device)
+    return op._dmask
+
+
+def _start(idx):
+    return idx.start if isinstance(idx, slice) else int(idx[0])
+
+
+class HostBackend:
+    """numpy buffers and a stand-in launch(case, bufs) -> bufs, as run_case() takes"""
+
+    def __init__(self, launch):
+        self.launch = launch
+
+    def initial(self, case):
+        return {op.name: op.z.copy() for op in case.ops}
+
+    def clone(self, bufs):
+        return {n: a.copy() for n, a in bufs.items()}
+
+
+class DeviceBackend:
+    """torch buffers that stay on the GPU: framed fields are laid out there from their compact node values, canaries
+    are filled there, and every comparison runs there"""
+
+    def initial(self, case):
+        import torch
+        TD = {"float32": torch.float32, "float64": torch.float64, "uint8": torch.uint8, "uint32": torch.int32}
+        bufs = {}
+        for op in case.ops:
+            tdt = TD[op.dtype.name]
+            if op._z is None and op.nodes is not None:
+                g = op.geo
+                t = torch.zeros(op.numel, dtype=tdt, device="cuda")
+                torch.as_strided(t, (g.B, g.H, g.W), (g.bs, g.ld, 1), g.ld + g.off).copy_(
+                    torch.from_numpy(np.ascontiguousarray(op.nodes)))
+            elif op._z is None and op.fill is not None:
+                t = torch.full((op.numel * op.dtype.itemsize,), op.fill, dtype=torch.uint8, device="cuda").view(tdt)
+            else:
+                t = torch.from_numpy(op.z.view(np.uint8)).cuda().view(tdt)
+            bufs[op.name] = t
+        return bufs
+
+    def clone(self, bufs):
+        return {n: t.clone() for n, t in bufs.items()}
+
+    def launch(self, case, bufs):
+        import torch
+        keep = _issue(case, {n: t.data_ptr() for n, t in bufs.items()})
+        torch.cuda.synchronize()
+        del keep
+        return bufs
+
+
+def sample_nodes(geo, b):
+    """flat indices of sample b's nodes"""
+    return (b * geo.bs + (np.arange(geo.H, dtype=np.int64)[:, None] + 1) * geo.ld + geo.off +
+            np.arange(geo.W, dtype=np.int64)[None, :]).ravel()
+
+
+def per_sample_inputs(case):
+    return [op for op in case.ops if op.role != "out" and op.sample is not None]
+
+
+def derive(top, top_bufs, case, bufs, src):
+    """The inputs of `case` (len(src) samples) become samples `src` of the top rung's: per-sample operands block by
+    block (a framed sample with its ghost rows and padding), shared ones (tables, pattern maps, counters) whole."""
+    assert case.B == len(src) and [o.name for o in case.ops] == [o.name for o in top.ops], (case, top)
+    for op, t in zip(case.ops, top.ops):
+        if op.role == "out":
+            continue
+        a, ta = bufs[op.name], top_bufs[op.name]
+        if op.sample is None:
+            assert op.numel == t.numel, (case, op.name)
+            a[:] = ta
+            continue
+        for i, b in enumerate(src):
+            a[_ix(a, op.sample(case.B, i))] = ta[_ix(ta, t.sample(top.B, b))]
+
+
+def check_ab(case, before, after):
+    """assertions (a), (b) and (d) of check() on one run: nothing outside the write set, inputs untouched, every
+    element of an output's write set stored (it no longer holds the canary)"""
+    for op in case.ops:
+        moved = _bits(after[op.name]) != _bits(before[op.name])
+        if op.role == "out" and not op.loose and bool((_mask(op, moved) & ~moved).any()):   # (d), on the canary
+            raise FootprintError("d", op.name, f"{case}: write-set element never stored at "
+                                 f"{op.where(_first(_mask(op, moved) & ~moved))}")
+        if op.role != "in":
+            moved = moved & ~_mask(op, moved)
+        if bool(moved.any()):
+            i = _first(moved)
+            raise FootprintError("b" if op.role == "in" else "a", op.name,
+                                 f"{case}: " + ("input modified" if op.role == "in" else "written outside the write "
+                                                                                          "set") + f" at {op.where(i)}")
+
+
+def partial_count(case, before, after):
+    """partial sums per sample behind the call's norms: the slots of its workspace that were stored to"""
+    for op in case.ops:
+        if op.norm in ("ws", "parts"):
+            return int((_bits(after[op.name]) != _bits(before[op.name])).sum()) // case.B
+    return None
+
+
+def sample_outputs(case, after, b, norms):
+    """[(operand, first raw index, values, write-set mask)] of sample b: fields and flat blocks (norms False), or the
+    per-sample norms and partial sets (norms True)"""
+    out = []
+    for op in case.ops:
+        if op.role == "in" or op.sample is None or (op.norm is not None) != norms:
+            continue
+        idx = op.sample(case.B, b)
+        a = after[op.name]
+        out.append((op, _start(idx), a[_ix(a, idx)], _mask(op, a)[_ix(a, idx)]))
+    return out
+
+
+def compare_samples(kind, what, ca, after_a, ba, cb, after_b, bb, norms=False):
+    """sample ba of case ca against sample bb of case cb: the same bytes on the write set"""
+    for (op, i0, va, ma), (_, _, vb, _) in zip(sample_outputs(ca, after_a, ba, norms),
+                                               sample_outputs(cb, after_b, bb, norms)):
+        if norms and va.shape != vb.shape:
+            if ca.entry.startswith(("pcg_", "fea_pcg_")):
+                raise FootprintError(kind, op.name, f"{what}: {va.shape[0]} against {vb.shape[0]} Krylov partials")
+            continue            # partial sets of different sizes: their sums are compared (compare_norms)
+        bad = (_bits(va) != _bits(vb)) & ma
+        if bool(bad.any()):
+            i = _first(bad)
+            raise FootprintError(kind, op.name, f"{what}: {int(bad.sum())} elements differ, first at "
+                                 f"{op.where(i0 + i)} ({va[i].item()!r} against {vb[i].item()!r})")
+
+
+def norm_values(case, after, b):
+    """{operand name: sample b's norm}; a partial set counts as the sum of its partials"""
+    return {op.name: float(_f64(v).sum().item()) if op.norm == "parts" else float(_f64(v)[0].item())
+            for op, _, v, _ in sample_outputs(case, after, b, True)}
+
+
+def compare_norms(case, seen):
+    """seen: [(rung label, partial count, {operand: value})] of ONE sample.  Sums of the same non-negative squares in
+    another order: equal partial counts -> the same bits; otherwise within 2 n u (relative) of each other, n the
+    nodes summed and u = 2^-53, the roundoff of the double every kernel accumulates its norm in."""
+    tol = 2.0 * case.norm_n * U_DOUBLE
+    for i, (la, na, va) in enumerate(seen):
+        for lb, nb, vb in seen[i + 1:]:
+            for name in va:
+                x, y = va[name], vb[name]
+                if not (np.isfinite(x) and np.isfinite(y)):
+                    raise FootprintError("h", name, f"{case}: non-finite norm {x!r} ({la}) / {y!r} ({lb})")
+                if na == nb and x != y:
+                    raise FootprintError("h", name, f"{case}: {la} and {lb} have {na} partials per sample but the "
+                                         f"norm differs: {x!r} against {y!r}")
+                if abs(x - y) > tol * max(abs(x), abs(y)):
+                    raise FootprintError("h", name, f"{case}: norm {x!r} ({la}, {na} partials) against {y!r} ({lb}, "
+                                         f"{nb} partials): relative difference above 2 n u = {tol:.3e}")
+
+
+def picks(B):
+    """first, middle and last sample"""
+    return sorted({0, B // 2, B - 1})
+
+
+def isolation(case, be, before=None, after=None):
+    """Run S for j first, middle, last: every node of sample j is a quiet NaN in every per-sample input (its scalars
+    row included; non-node storage as in run Z) and every other sample's outputs keep run Z's bytes.  Then, where the
+    call produces norms: one NaN at an interior node of the field the norm is of makes sample j's norms non-finite."""
+    if before is None:
+        before = be.initial(case)
+        after = be.launch(case, be.clone(before))
+    for j in picks(case.B):
+        bufs = be.clone(before)
+        for op in per_sample_inputs(case):
+            a = bufs[op.name]
+            idx = sample_nodes(op.geo, j) if op.geo is not None else op.sample(case.B, j)
+            a[_ix(a, idx)] = float("nan")
+        got = be.launch(case, bufs)
+        for b in range(case.B):
+            if b != j:
+                for norms in (False, True):
+                    compare_samples("s", f"{case}: sample {b} with sample {j} all NaN", case, got, b, case, after, b,
+                                    norms)
+        if case.nan_op is None:
+            continue
+        bufs = be.clone(before)
+        op = next(o for o in case.ops if o.name == case.nan_op)
+        g = op.geo
+        bufs[op.name][j * g.bs + (1 + (g.H // 2 - 1) // 2 + 1) * g.ld + g.off + g.W - 2] = float("nan")
+        got = be.launch(case, bufs)
+        vals = norm_values(case, got, j)
+        assert vals, case
+        for name, v in vals.items():
+            if np.isfinite(v):
+                raise FootprintError("n", name, f"{case}: sample {j} has a NaN node in {op.name} but its norm is {v!r}")
+
+
+def run_ladder(build, rungs, be, isolate_at=4):
+    """build(B) -> the case for B samples.  Runs the top rung, every lower rung as its prefix and the last sample
+    alone; asserts (a), (b) on every run, 'h' between rungs, and the isolation checks on the rung of isolate_at
+    samples.  -> [(label, partial count)] for the report."""
+    top = build(rungs[-1])
+    before = be.initial(top)
+    after = be.launch(top, be.clone(before))
+    check_ab(top, before, after)
+    ntop = partial_count(top, before, after)
+    seen = {b: [(f"B={top.B}", ntop, norm_values(top, after, b))] for b in range(top.B)}
+    report = [(f"B={top.B}", ntop)]
+    if top.B == isolate_at:
+        isolation(top, be, before, after)
+    for src in [tuple(range(k)) for k in rungs[:-1]] + [(top.B - 1,)]:
+        label = f"B={len(src)}" + (" (last sample alone)" if src[0] else "")
+        case = build(len(src))
+        b0 = be.initial(case)
+        derive(top, before, case, b0, src)
+        a0 = be.launch(case, be.clone(b0))
+        check_ab(case, b0, a0)
+        n = partial_count(case, b0, a0)
+        report.append((label, n))
+        for i, b in enumerate(src):
+            what = f"{case}: sample {b} in {label} against B={top.B}"
+            compare_samples("h", what, case, a0, i, top, after, b)
+            if n == ntop or case.entry.startswith(("pcg_", "fea_pcg_")):
+                compare_samples("h", what, case, a0, i, top, after, b, norms=True)
+            seen[b].append((label, n, norm_values(case, a0, i)))
+        if len(src) == isolate_at and not src[0]:
+            isolation(case, be, b0, a0)
+    for b, s in seen.items():
+        if s[0][2]:
+            compare_norms(top, s)
+    return report

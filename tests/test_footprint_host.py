@@ -223,3 +223,139 @@ def test_dd_cases_against_the_record_model(suf):
             fp.run_case(c, dd_model)
             dst = next(o for o in c.ops if o.name == "dst")
             assert dst.mask.sum() == sum(h * w for _, _, h, w in rec) and not dst.mask.all()
+
+
+# ----------------------------------------------------------------------------- task-height ladders
+def test_pick_rb_restatement_matches_the_abi():
+    """The coverage guard's restatement of pick_rb against what the ABI exposes: fea_pcg_parts is nstrips x the row
+    tasks of ONE sample at pick_rb's height, over a sweep of shapes that reaches every height; and the cycle join's
+    partial count (fea_mg_join_norm_parts, which takes B because its height depends on it) differs between the
+    ladder's rungs 1, 4 and 16."""
+    from feanet_amd import _lib
+    L = _lib.lib()
+    heights = set()
+    for esz in (4, 8):
+        for H in (3, 5, 33, 129, 1025, 4097, 4099, 8193, 16385, 32769, 65537, 100001):
+            for W in (3, 33, 163, 257, 259, 321, 515, 1025, 4097):
+                ns = fp.nstrips(W, esz)
+                rb = fp.pick_rb(1, ns, H - 2)
+                heights.add(rb)
+                assert L.fea_pcg_parts(H, W, esz) == ns * -(-(H - 2) // rb), (H, W, esz, rb)
+        per = [L.fea_mg_join_norm_parts(B, fp.LADDER_H, fp.LADDER_W, esz) for B in (1, 4, 16)]
+        assert len(set(per)) == 3 and min(per) > 0, per
+    assert heights == {2, 4, 8, 16, 32}
+    assert [fp.pick_rb(1, 1, H - 2) for H in (4097, 8193, 16385, 32769, 65537)] == [2, 4, 8, 16, 32]
+    assert fp.pick_rb(1, 1, 131073 - 2, 64) == 64
+
+
+def test_ladders_reach_their_heights():
+    """five distinct heights on the batch ladder, six for the two kernels whose cap is 64 rows; a ladder that lost a
+    height (kTargetWaves or kRB changed) says so"""
+    for entry in fp.DESC:
+        if entry in fp.BATCH_FREE or entry in fp.DD_NAMES:
+            continue
+        for esz in (4, 8):
+            hs = fp.ladder_heights(entry, esz)
+            if entry.startswith(("pcg_", "fea_pcg_")):
+                assert set(hs) == {2}
+            else:
+                assert hs == [2, 4, 8, 16, 32] + ([64] if entry in fp.CAP64 else [])
+    assert sorted(fp.CAP64) == ["mg_cycle_join", "mg_sweep_restrict"]
+    old = fp.K_TARGET_WAVES
+    try:
+        fp.K_TARGET_WAVES = 4096
+        with pytest.raises(AssertionError, match="re-pick the ladder"):
+            fp.ladder_heights("mg_sweep", 8)
+    finally:
+        fp.K_TARGET_WAVES = old
+
+
+# a numpy stand-in for a framed kernel with a fused norm, run in row tasks whose height grows with the batch:
+# out(interior) = 2 u + f, norm[b] = sqrt(sum of u^2 over the interior), one partial per task in ws
+LH, LW = 19, 9
+
+
+def ladder_case(B):
+    g = fp.Geo(LH, LW, B, 8)
+    rng = np.random.default_rng(B)
+    c = fp.Case("stand_in", "f64", f"{LH}x{LW} B={B}")
+    c.B, c.norm_n, c.nan_op = B, (LH - 2) * (LW - 2), "u"
+    c.add(fp.field_in("u", g, np.float64, rng.standard_normal((B, LH, LW))))
+    c.add(fp.field_in("f", g, np.float64, rng.standard_normal((B, LH, LW))))
+    c.add(fp.field_out("out", g, np.float64, g.interior()))
+    c.add(fp.flat_out("ws", 10 * B + 3, np.float64, np.arange(10 * B + 3) < 10 * B, loose=True, norm="ws"))
+    c.add(fp.flat_out("norm", B + 2, np.float64, np.arange(B + 2) < B, sample=fp.rows(1), norm="norm"))
+    return c, g
+
+
+def ladder_stand_in(fault=None):
+    def launch(case, bufs):
+        B = case.B
+        g = fp.Geo(LH, LW, B, 8)
+        u, f, out, ws, norm = (bufs[n] for n in ("u", "f", "out", "ws", "norm"))
+        rb = 2 * B                                           # the task height: 2, 4, 8 rows on the rungs 1, 2, 4
+        cols = np.arange(1, LW - 1)
+        for b in range(B):
+            starts = list(range(1, LH - 1, rb))
+            for t, r0 in enumerate(starts):
+                rows = np.arange(r0, min(r0 + rb, LH - 1))
+                i = g.index(rows, cols)[b].ravel()
+                out[i] = 2 * u[i] + f[i]
+                if fault == "height" and t:                  # a task's first row takes its halo row from the wrong place
+                    j = g.index(rows[:1], cols)[b].ravel()
+                    out[j] += 1e-9 * u[j - g.ld]
+                sq = u[i] ** 2
+                ws[b * len(starts) + t] = np.nansum(sq) if fault == "nan dropped" else sq.sum()
+            if fault == "leak" and b + 1 < B:                # 0 * (a node of the next sample)
+                j = g.index([2], [2])
+                out[j[b]] += 0 * u[j[b + 1]]
+            norm[b] = np.sqrt(ws[b * len(starts):(b + 1) * len(starts)].sum())
+            if fault == "norm height":
+                norm[b] *= 1 + 1e-9 * rb
+        return bufs
+    return launch
+
+
+def test_correct_ladder_stand_in_passes():
+    report = fp.run_ladder(lambda B: ladder_case(B)[0], (1, 2, 4), fp.HostBackend(ladder_stand_in()))
+    assert [n for _, n in report] == [3, 9, 5, 9]           # partials per sample: B=4 (top), B=1, B=2, last alone
+    fp.isolation(ladder_case(3)[0], fp.HostBackend(ladder_stand_in()))
+
+
+@pytest.mark.parametrize("fault,kind,operand", [("height", "h", "out"), ("norm height", "h", "norm"),
+                                                ("leak", "s", "out"), ("nan dropped", "n", "norm")])
+def test_ladder_fault_is_reported_by_its_assertion(fault, kind, operand):
+    """a result that depends on the task height, a norm that does, a leak between samples and a NaN that a norm
+    drops each raise the error kind meant for them"""
+    with pytest.raises(fp.FootprintError) as e:
+        fp.run_ladder(lambda B: ladder_case(B)[0], (1, 2, 4), fp.HostBackend(ladder_stand_in(fault)))
+    assert (e.value.kind, e.value.operand) == (kind, operand), str(e.value)
+
+
+def test_prefix_rungs_hold_the_top_rungs_samples():
+    """derive(): a lower rung's per-sample operands are the top rung's samples block by block (ghost rows and
+    padding included), shared operands whole; flat [B, per] operands and the gathered source's rank-major blocks
+    follow their own layouts"""
+    be = fp.HostBackend(None)
+    for entry, shape, mode in (("mg_pack", (33, 321), ""), ("mg_mid_down_gathered", (13, 13), "k 1 T 4 4"),
+                               ("pcg_update", (33, 321), ""), ("fea_pcg_update_f64f32", (33, 321), "")):
+        suf = "f64"
+        top = fp.build_case(entry, suf, shape + (3,), True if entry != "mg_pack" else False, mode)
+        tb = be.initial(top)
+        for src in ((0,), (0, 1), (2,)):
+            c = fp.build_case(entry, suf, shape + (len(src),), True if entry != "mg_pack" else False, mode)
+            b = be.initial(c)
+            fp.derive(top, tb, c, b, src)
+            for op, t in zip(c.ops, top.ops):
+                if op.role == "out":
+                    continue
+                if op.sample is None:
+                    assert np.array_equal(b[op.name], tb[op.name])
+                    continue
+                assert op.name in ("src", "bc", "gsrc", "scalars", "sb") or op.geo is not None, op.name
+                for i, s in enumerate(src):
+                    assert np.array_equal(b[op.name][op.sample(c.B, i)], tb[op.name][t.sample(3, s)], equal_nan=True)
+        if entry == "mg_mid_down_gathered":       # [Pr * Pc][B][gcr][gcc]
+            gs = next(o for o in top.ops if o.name == "gsrc")
+            v = gs.z.reshape(4, 3, 6 * 6)
+            assert np.array_equal(gs.z[gs.sample(3, 1)], v[:, 1].ravel())

@@ -18,7 +18,8 @@ def npdt(T):
 
 @pytest.mark.parametrize("T", [torch.float32, torch.float64])
 @pytest.mark.parametrize("problem", ["poisson", "interface"])
-@pytest.mark.parametrize("m,n,B", [(32, 32, 2), (64, 64, 1), (16, 256, 1), (300, 130, 2), (128, 128, 3)])
+@pytest.mark.parametrize("m,n,B", [(32, 32, 2), (64, 64, 1), (16, 256, 1), (300, 130, 2), (128, 128, 3),
+                                   (16384, 32, 1)])      # (one strip, 16383 rows: tall row tasks)
 @pytest.mark.parametrize("zero", [False, True])
 def test_hsweep_vs_oracle(T, problem, m, n, B, zero):
     from feanet_amd import _lib, mesh_setup as ms

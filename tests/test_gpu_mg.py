@@ -555,7 +555,9 @@ def test_coarse_tail_kernel(T, problem, Nt, nlev, B, nu):
 
 
 # ----------------------------------------------------------------------------- rectangles (H != W)
-RECT = [(8, 16, 1), (64, 16, 2), (16, 256, 1), (512, 128, 1), (6, 10, 3)]
+# (65536, 32, 1) and (4096, 32, 8): one strip and >= 2048 row tasks, so the task height is 32 and 16 rows (every
+# other shape of the list runs at 2; tests/footprint.py ties the heights in between to these bitwise)
+RECT = [(8, 16, 1), (64, 16, 2), (16, 256, 1), (512, 128, 1), (6, 10, 3), (65536, 32, 1), (4096, 32, 8)]
 
 
 @pytest.mark.parametrize("T", [torch.float32, torch.float64])
@@ -807,7 +809,9 @@ def test_cycle_join_kernel_direct(nt):
     boundary nodes that are not zero (Dirichlet data) and a coarse correction with a nonzero ring."""
     from feanet_amd import _lib
     for T in (torch.float64, torch.float32):
-        for (m, n, B, problem) in ((256, 256, 2, "poisson"), (130, 514, 1, "poisson"), (64, 64, 1, "interface")):
+        # (4096, 32, 16): the join's power-of-two path (B >= kJoinBatchPow2) at 32-row tasks
+        for (m, n, B, problem) in ((256, 256, 2, "poisson"), (130, 514, 1, "poisson"), (64, 64, 1, "interface"),
+                                   (4096, 32, 16, "poisson")):
             fr = Frame(n, B, T, problem, m=m)
             co = Frame(n // 2, B, T, problem, m=m // 2)
             ktab, omd, R, P, kt, om, rt, pt = tables(problem, T, learned=(problem == "interface"))

@@ -52,7 +52,9 @@ class Fields:
         if problem == "interface":
             # a rectangle is a window of the square's map around the inclusion, as a domain-decomposed rank's
             full = ms.interface_pattern_map(n + 1)
-            r0 = (n - m) // 2
+            if m > n:      # a tall grid: the square's map repeated down the rows (any map of valid ids is a problem)
+                full = full[np.arange(m + 1) % (n + 1)]
+            r0 = max(n - m, 0) // 2
             self.pid_np = np.ascontiguousarray(full[r0:r0 + m + 1])
         else:
             self.pid_np = np.zeros((self.H, self.W), np.uint8)
@@ -106,7 +108,21 @@ def dot64(a, b):
     return (a * b).reshape(a.shape[0], -1).sum(1)
 
 
-SIZES = [(2, None, 1), (4, None, 3), (16, None, 3), (128, None, 1), (256, None, 3), (160, 24, 2)]
+SIZES = [(2, None, 1), (4, None, 3), (16, None, 3), (128, None, 1), (256, None, 3), (160, 24, 2),
+         (32, 4096, 2), (32, 16384, 1), (32, 65536, 1)]
+# the tall one-strip shapes and the row-task height they must reach (every other size runs 2-row tasks)
+TALL = {(32, 4096): 2, (32, 16384): 8, (32, 65536): 32}
+
+
+def task_height(H, W, esz):
+    """the rows per task behind fea_pcg_parts on a one-strip grid: the only height with that many row tasks"""
+    from feanet_amd import _lib
+    per = int(_lib.lib().fea_pcg_parts(H, W, esz))
+    hs = [rb for rb in (2, 4, 8, 16, 32) if -(-(H - 2) // rb) == per]
+    assert len(hs) == 1, (H, W, per)
+    return hs[0]
+
+
 # (T, n, rows, B); 512 is the fp32 two-strip size (fp64 crosses its strip edge at 256)
 KERNEL_CASES = [(T, n, m, B) for T in (torch.float32, torch.float64) for n, m, B in SIZES] + \
     [(torch.float32, 512, None, 1)]
@@ -122,6 +138,8 @@ def test_kernels_vs_numpy(T, problem, n, m, B, nt):
     rng = np.random.default_rng(1000 * n + B)
     fr = Fields(n, B, T, problem, m=m)
     g = fr.L.geom()
+    if (n, m) in TALL:
+        assert task_height(fr.H, fr.W, 4 if T == torch.float32 else 8) == TALL[(n, m)]
 
     # --- residual: r = f - K x inside, 0 on the boundary; also with r aliasing f
     x, f = fr.rand(rng, interior=False), fr.rand(rng, interior=False)

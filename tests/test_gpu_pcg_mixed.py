@@ -64,7 +64,9 @@ class Fields:
         self.ktab = ms.stencil_table(prop if problem == "interface" else None)
         if problem == "interface":
             full = ms.interface_pattern_map(n + 1)
-            r0 = (n - m) // 2
+            if m > n:      # a tall grid: the square's map repeated down the rows (any map of valid ids is a problem)
+                full = full[np.arange(m + 1) % (n + 1)]
+            r0 = max(n - m, 0) // 2
             self.pid_np = np.ascontiguousarray(full[r0:r0 + m + 1])
         else:
             self.pid_np = np.zeros((self.H, self.W), np.uint8)
@@ -134,7 +136,10 @@ class Fields:
 
 # (n, rows, B): 256 crosses the fp64 strip edge (128 columns); 512 crosses the fp32 frame's strip width (256), so four
 # fp64 strips index one fp32 row; (160, 24) is a rectangle
-SIZES = [(2, None, 1), (4, None, 3), (16, None, 3), (128, None, 1), (256, None, 3), (160, 24, 2), (512, None, 1)]
+SIZES = [(2, None, 1), (4, None, 3), (16, None, 3), (128, None, 1), (256, None, 3), (160, 24, 2), (512, None, 1),
+         (32, 4096, 2), (32, 16384, 1), (32, 65536, 1)]
+# the tall one-strip shapes and the row-task height they must reach (every other size runs 2-row tasks)
+TALL = {(32, 4096): 2, (32, 16384): 8, (32, 65536): 32}
 
 
 @pytest.mark.parametrize("problem", ["poisson", "interface"])
@@ -146,6 +151,9 @@ def test_kernels_vs_numpy(problem, n, m, B, nt):
     rng = np.random.default_rng(1000 * n + B)
     fr = Fields(n, B, problem, m=m)
     g = fr.geom()
+    if (n, m) in TALL:
+        from test_gpu_pcg import task_height
+        assert task_height(fr.H, fr.W, 8) == TALL[(n, m)]
     cr = lambda name, *a: _lib.call_raw(name, *a, None)
 
     # --- narrow: s_b from the sample's RNORM (whatever its magnitude), r32 = float32(r s_b) on the interior
