@@ -516,7 +516,15 @@ size_t fea_mg_hjac_tail_lds_bytes(int Ht, int Wt, int nlev, int elem_size, int m
  *   (:177-181, one fea_mg_prolong_sweep(u = NULL) per level): reads f[0..k-1] = f_a .. f_{a+k-1},
  *   writes out = u_a (interior nodes only: the boundary nodes of out are not written, and taken as zero, as
  *   in every level below the finest); intermediate iterates are not stored.  Tile TR x TC of level a.
- * Both return FEA_EINVAL if the tile's LDS footprint (fea_mg_mid_lds_bytes) does not fit. */
+ * Both return FEA_EINVAL if the tile's LDS footprint (fea_mg_mid_lds_bytes) does not fit.
+ * Register-strip form (mid_down and mid_up, not mid_down_gathered): TR = -u (u >= 1), TC = -1 runs k = 3 levels of
+ * a one-pattern problem (FEA_EINVAL for any other k or ntab > 1) as overlapped register strips like
+ * fea_mg_zero_restrict2 / fea_mg_prolong2 carried one level further — no LDS, no barrier, every wave task independent:
+ * the form for the three launch-bound levels (at most 513^2 at batch 1) right above the coarse tail, where a launch
+ * costs a fixed ~5 us whatever it does.  A task is u units tall (a unit: one row of level a+3 going down, four rows
+ * of level a going up); the results do not depend on u and are bitwise the tiled form's and the per-level kernels'.
+ * Same reference lines as above, at three consecutive levels (MultiGrid.Step's recursion and its unwinding, mg_test
+ * :27352-27372). */
 int fea_mg_mid_down_f32(const float* const* f, const uint8_t* const* pid, int k, int B, int H, int W,
                         const float* ktab, const float* omd, int ntab, const float* rtab, int nrtab, float w0,
                         int TR, int TC, void* stream);

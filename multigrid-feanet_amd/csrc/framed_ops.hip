@@ -1861,6 +1861,585 @@ __global__ __launch_bounds__(256) void k_mg_prolong2(MgArgs<T> g) {
 }
 
 // ---------------------------------------------------------------------------
+// Three-level register kernels (the launch-bound levels right above the coarse tail): the two-level kernels' form
+// carried one level further.  Single pattern only (the launch layer refuses ntab > 1), top-down tasks only: one
+// body each, these kernels start cold every cycle.  A level's values sit one (fp32 at level l+1: two) per lane; from
+// level l+2 on in fp64 only every second (then fourth) lane holds one, and its column neighbours are SH lanes away.
+// ---------------------------------------------------------------------------
+template <typename T>
+struct Mg3Args {
+  MgArgs<T> g;   // levels l, l+1 (Hc ..) and l+2 (Hc2 ..) as in the two-level kernels
+  T* out3;       // k_mg_zero_restrict3: f_{l+3}
+  const T* ec3;  // k_mg_prolong3: the correction of level l+3
+  int Hc3, Wc3, ldc3;
+  long long bsc3;
+};
+
+template <int SH, typename T>
+__device__ __forceinline__ T shrz(T x) {  // lane i receives lane i-SH's value, 0 at the wave edge
+#pragma unroll
+  for (int k = 0; k < SH; ++k) x = shr1z(x);
+  return x;
+}
+template <int SH, typename T>
+__device__ __forceinline__ T shlz(T x) {
+#pragma unroll
+  for (int k = 0; k < SH; ++k) x = shl1z(x);
+  return x;
+}
+template <typename T, int N, int SH>
+__device__ __forceinline__ Row<T, N> own_row_sh(const T (&x)[N]) {  // own_row with the neighbours SH lanes away
+  Row<T, N> w;
+#pragma unroll
+  for (int k = 0; k < N; ++k) w.a[k + 1] = x[k];
+  w.a[0] = shrz<SH>(x[N - 1]);
+  w.a[N + 1] = shlz<SH>(x[0]);
+  return w;
+}
+
+// One in-register zero-guess restriction stage (k_mg_zero_restrict2's second stage as a value): rows of a level's
+// right-hand side are pushed top-down, N columns per lane (N = 2: an odd column and the even one right of it; N = 1:
+// one column, the coarse nodes on the lanes whose column is even); an even row closes the coarse row centred on
+// the row before it and push() returns that row's value on the lane's coarse column.  Nothing guards the first rows:
+// the windows start as zeros, so the first row closed is not a value of the grid, and its caller drops it.
+template <typename T, int N, int SH>
+struct RStage {
+  static constexpr int B0 = N == 1 ? 0 : 1;  // window index of column 2M-1 of the lane's coarse column M
+  Row<T, N> Va{}, Vb{}, Vc{};                // v = omd f of the last three rows pushed (Va oldest)
+  Row<T, N> Ro{}, Re{};                      // the last odd / even residual rows
+  T fp[N] = {};                              // the right-hand side of the row pushed before
+
+  // rin: the row is interior; jin: the lane's columns are
+  template <bool ODD>
+  __device__ __forceinline__ T push(const T (&o)[N], bool rin, const bool (&jin)[N], const T (&ks)[9],
+                                    const T (&rs)[9], T om, T w0) {
+    T x[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) x[q] = (rin && jin[q]) ? om * o[q] : T(0);
+    Va = Vb;
+    Vb = Vc;
+    Vc = own_row_sh<T, N, SH>(x);
+    const PRow<N> np{};
+    T r[N];  // residual of the row pushed before
+#pragma unroll
+    for (int q = 0; q < N; ++q) r[q] = fp[q] - kapply<T, N, false>(Va, Vb, Vc, np, np, np, q, ks, nullptr);
+    const Row<T, N> R = own_row_sh<T, N, SH>(r);
+    T out = T(0);
+    if constexpr (!ODD) {
+      const int zp[1] = {0};
+      const T acc = restrict9<T, false>(rs, nullptr, Ro.a, Re.a, R.a, B0, zp, zp, zp, 0);
+      out = w0 * acc;
+      Ro = R;
+    } else {
+      Re = R;
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q) fp[q] = o[q];
+    return out;
+  }
+};
+
+// ---------------------------------------------------------------------------
+// Three zero-guess restrictions in one pass (levels l, l+1, l+2 going down into the coarse tail):
+//   v = omd f_l; f_{l+1} = w0 R(f_l - K v);  v' = omd f_{l+1}; f_{l+2} = w0 R(f_{l+1} - K v');  the same once more
+// k_mg_zero_restrict2 with a third stage fed from the second one's values in registers.  All three outputs are
+// stored (the up pass recomputes its iterates from them), none is read back.  One owned row K of f_{l+3} needs
+// f_{l+2} rows 2K-2 .. 2K+2, f_{l+1} rows 4K-6 .. 4K+6, f_l rows 8K-14 .. 8K+14: a task owning u rows streams 8u + 21.
+// Every node value is the expression of k_mg_zero_restrict in its order, so the outputs are bitwise three
+// single-level launches (tests/test_gpu_three_level.py).
+// Exact lanes, from the shifts (0 comes in at the wave edge): a residual needs v one column left and right, a coarse
+// value three residual columns: f_{l+1} is exact on lanes 1 .. 62; stage 2 shifts by one lane: f_{l+2} on 3 .. 60
+// (fp32, two columns per lane: 2 .. 60); stage 3 shifts by SH3 lanes: f_{l+3} on L3 .. H3.
+// ---------------------------------------------------------------------------
+template <typename T>
+struct OvlZ3 {
+  static constexpr int V = Frame<T>::VEC;
+  static constexpr int Q = V / 2;
+  static constexpr int SH3 = Q == 1 ? 2 : 1;  // lanes between two f_{l+2} columns
+  static constexpr int LN = 2 * SH3;          // lanes between two f_{l+3} columns
+  static constexpr int L1 = 1, H1 = 62;
+  static constexpr int L2 = L1 + (Q == 1 ? 2 : 1), H2 = H1 - 2;
+  static constexpr int L3 = L2 + 2 * SH3, H3 = H2 - 2 * SH3;
+  static constexpr int I0 = L3;                  // lane of the strip's first owned f_{l+3} column
+  static constexpr int NC = (H3 - I0) / LN + 1;  // owned f_{l+3} columns per strip (fp64 13, fp32 28)
+  static constexpr int S = 8 * NC;               // owned fine columns per strip (fp64 104, fp32 224)
+  // the strip's first owned f_{l+2} column (2 Nlo - 1) sits SH3 lanes left of I0, its first owned f_{l+1} column
+  // (4 Nlo - 3) three lanes (fp32: one lane) left; the last owned columns of all three levels on the last owning lane
+  static_assert(I0 - SH3 >= L2 && I0 - (Q == 1 ? 3 : 1) >= L1 && I0 + LN * (NC - 1) <= H3, "owned lanes are exact");
+  // lane 0's first column, 8 - (V - 1) - V I0 in strip 0, lies inside the frame left of column 0
+  static_assert(V * I0 + V - 1 - 8 <= Frame<T>::OFF, "the left halo fits the frame");
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_mg_zero_restrict3(Mg3Args<T> a) {
+  using F = Frame<T>;
+  using O = OvlZ3<T>;
+  constexpr int V = F::VEC;
+  constexpr int Q = O::Q;
+  const MgArgs<T>& g = a.g;
+  const TaskId id = decode_task_lin(g.nstrips, g.ntr);
+  if (!id.valid) return;
+  const int lane = lane_id();
+  const int H = g.H, W = g.W, Hc = g.Hc, Wc = g.Wc, Hc2 = g.Hc2, Wc2 = g.Wc2, Hc3 = a.Hc3, Wc3 = a.Wc3;
+  // owned columns of f_{l+3}, f_{l+2}, f_{l+1}
+  const int Nlo = id.s * O::NC + 1, Nhi = Nlo + O::NC;
+  const int Mlo = 2 * Nlo - 1, Mhi = 2 * Nhi - 1;
+  const int Jlo = 2 * Mlo - 1, Jhi = 2 * Mhi - 1;
+  const int cs = 8 * Nlo - (V - 1) - V * O::I0;  // first loaded column: lane I0's first column is 8 Nlo - (V - 1)
+  const int cl = cs + V * lane;                  // odd
+  const int J0 = (cl + 1) / 2;                   // the lane's first column of level l+1
+  const int M0 = Q == 1 ? (J0 >> 1) : ((J0 + 1) >> 1);  // its column of level l+2 (fp64: on the lanes of even J0)
+  const int N0 = M0 >> 1;                               // its column of level l+3 (on the lanes of even M0)
+  const bool has2 = Q == 1 ? !(J0 & 1) : true;
+  const bool has3 = has2 && !(M0 & 1);
+  // owned rows of f_{l+3}, f_{l+2}, f_{l+1}
+  const int K0 = 1 + id.t * (g.rb / 8);
+  const int K1 = min(K0 + g.rb / 8, Hc3 - 1);
+  const bool last = K1 == Hc3 - 1;
+  const int R2lo = 2 * K0 - 1, R2hi = last ? Hc2 - 1 : 2 * K1 - 1;
+  const int R1lo = 2 * R2lo - 1, R1hi = last ? Hc - 1 : 2 * R2hi - 1;
+  T ks[9], rs[9];
+#pragma unroll
+  for (int d = 0; d < 9; ++d) {
+    ks[d] = g.ktab[d];
+    rs[d] = g.rtab[d];
+  }
+  const T om = g.omd[0];
+  const T w0 = g.w;
+  bool cin[V], jin[Q], st1[Q];
+#pragma unroll
+  for (int k = 0; k < V; ++k) cin[k] = cl + k >= 1 && cl + k <= W - 2;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    jin[q] = J0 + q >= 1 && J0 + q <= Wc - 2;
+    st1[q] = J0 + q >= Jlo && J0 + q < Jhi && J0 + q <= Wc - 2;
+  }
+  const bool min2[1] = {M0 >= 1 && M0 <= Wc2 - 2};
+  const bool st2 = has2 && M0 >= Mlo && M0 < Mhi && M0 <= Wc2 - 2;
+  const bool st3 = has3 && N0 >= Nlo && N0 < Nhi && N0 <= Wc3 - 2;
+  const T* __restrict__ fb = g.f + (long long)id.b * g.bs + F::OFF + cs;
+  T* __restrict__ cb = g.out + (long long)id.b * g.bsc + F::OFF + J0;
+  T* __restrict__ cb2 = g.out2 + (long long)id.b * g.bsc2 + F::OFF + M0;
+  T* __restrict__ cb3 = a.out3 + (long long)id.b * a.bsc3 + F::OFF + N0;
+  const int ld = g.ld;
+  const int ll = min(lane, (W - 1 - cs) / V);  // lanes past the grid re-read the last needed line
+  auto rowo = [&](int r) -> long long { return (long long)(min(max(r, -1), H) + 1) * ld + V * ll; };
+
+  // ---- stage 1 (level l): the rows of k_mg_zero_restrict
+  struct In {
+    T f[V];
+  };
+  struct Wn {
+    Row<T, V> v;
+    T f[V];
+  };
+  auto load = [&](int y) {
+    In r;
+    vload<T, V>(fb + rowo(y), r.f);
+    return r;
+  };
+  auto mk = [&](const In& r, int y) {
+    Wn w;
+    const bool rin = y >= 1 && y <= H - 2;
+    T x[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      x[k] = (rin && cin[k]) ? om * r.f[k] : T(0);
+      w.f[k] = r.f[k];
+    }
+    w.v = own_row<T, V>(x);
+    return w;
+  };
+  const PRow<V> np{};
+  const int zp[1] = {0};
+  auto resid = [&](const Wn& x0, const Wn& x1, const Wn& x2, T (&r)[V + 1]) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) r[k] = x1.f[k] - kapply<T, V, false>(x0.v, x1.v, x2.v, np, np, np, k, ks, nullptr);
+    r[V] = shl1z(r[0]);
+  };
+
+  // f_{l+1} rows Ia .. 4 K1 + 2: the first one from its own loads, then four per loop body out of a ring of eight
+  // fine rows (two per row, consumed in place and refilled eight fine rows ahead)
+  const int Ia = 4 * K0 - 6;
+  const In i0 = load(2 * Ia - 2), i1 = load(2 * Ia - 1), i2 = load(2 * Ia);
+  const In p0 = load(2 * Ia + 1), p1 = load(2 * Ia + 2);
+  In ring[4][2];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    ring[d][0] = load(2 * (Ia + 1 + d) + 1);
+    ring[d][1] = load(2 * (Ia + 1 + d) + 2);
+  }
+  Wn X0 = mk(i0, 2 * Ia - 2), X1 = mk(i1, 2 * Ia - 1), X2 = mk(i2, 2 * Ia);
+  T Rp[V + 1], Rm[V + 1], Rn[V + 1];  // residual rows 2I-1 (carried), 2I, 2I+1 of the current row I
+  resid(X0, X1, X2, Rp);
+  auto step = [&](const In& r, int y, T (&R)[V + 1]) {  // fine row y enters the window: the residual of row y-1
+    X0 = X1;
+    X1 = X2;
+    X2 = mk(r, y);
+    resid(X0, X1, X2, R);
+  };
+  auto finish1 = [&](int I, T (&o)[Q]) {  // f_{l+1} row I from Rp, Rm, Rn; owned rows and columns are stored
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const T acc = restrict9<T, false>(rs, nullptr, Rp, Rm, Rn, 2 * q, zp, zp, zp, 0);
+      o[q] = w0 * acc;
+    }
+    if (I >= R1lo && I < R1hi) {
+      T* cp = cb + (long long)(I + 1) * g.ldc;
+#pragma unroll
+      for (int q = 0; q < Q; ++q)
+        if (st1[q]) cp[q] = o[q];
+    }
+#pragma unroll
+    for (int k = 0; k <= V; ++k) Rp[k] = Rn[k];
+  };
+  auto row1 = [&](int I, auto slot, T (&o)[Q]) {
+    constexpr int SL = decltype(slot)::value;
+    step(ring[SL][0], 2 * I + 1, Rm);
+    ring[SL][0] = load(2 * I + 9);
+    step(ring[SL][1], 2 * I + 2, Rn);
+    ring[SL][1] = load(2 * I + 10);
+    finish1(I, o);
+  };
+  auto in1 = [&](int I) { return I >= 1 && I <= Hc - 2; };
+  auto in2 = [&](int Kr) { return Kr >= 1 && Kr <= Hc2 - 2; };
+
+  RStage<T, Q, 1> s2;        // level l+1 -> f_{l+2}
+  RStage<T, 1, O::SH3> s3;   // level l+2 -> f_{l+3}
+  auto row2 = [&](int Kr, T o2, auto odd_c) {  // f_{l+2} row Kr: store what is owned, push it to stage 3
+    if (st2 && Kr >= R2lo && Kr < R2hi) cb2[(long long)(Kr + 1) * g.ldc2] = o2;
+    const T x[1] = {o2};
+    return s3.template push<decltype(odd_c)::value>(x, in2(Kr), min2, ks, rs, om, w0);
+  };
+  T o[Q];
+  step(p0, 2 * Ia + 1, Rm);
+  step(p1, 2 * Ia + 2, Rn);
+  finish1(Ia, o);
+  s2.template push<false>(o, in1(Ia), jin, ks, rs, om, w0);  // the first even row closes nothing
+  // body K: f_{l+1} rows 4K+3 .. 4K+6, which close f_{l+2} rows 2K+1 and 2K+2, the latter f_{l+3} row K.  K runs from
+  // K0 - 2: the row the first body closes first (2 K0 - 3) is not a value of the grid (RStage) and its owner is the
+  // task above; stage 3 takes it as its first row, which only the row it closes first (K0 - 1, dropped) reads
+  int I = Ia + 1;
+  for (int K = K0 - 2; K < K1; ++K, I += 4) {
+    row1(I, std::integral_constant<int, 0>{}, o);
+    s2.template push<true>(o, in1(I), jin, ks, rs, om, w0);
+    row1(I + 1, std::integral_constant<int, 1>{}, o);
+    T o2 = s2.template push<false>(o, in1(I + 1), jin, ks, rs, om, w0);
+    row2(2 * K + 1, o2, std::true_type{});
+    row1(I + 2, std::integral_constant<int, 2>{}, o);
+    s2.template push<true>(o, in1(I + 2), jin, ks, rs, om, w0);
+    row1(I + 3, std::integral_constant<int, 3>{}, o);
+    o2 = s2.template push<false>(o, in1(I + 3), jin, ks, rs, om, w0);
+    const T o3 = row2(2 * K + 2, o2, std::false_type{});
+    if (st3 && K >= K0) cb3[(long long)(K + 1) * a.ldc3] = o3;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Three recomputed-iterate prolongations in one pass (levels l+2, l+1, l going up out of the coarse tail):
+//   x'' = omd f_{l+2} + w1 P(e_{l+3});  u'' = J(x'', f_{l+2});  x' = omd f_{l+1} + w1 P(u'');  u' = J(x', f_{l+1});
+//   x = omd f_l + w1 P(u');  out = J(x, f_l)
+// k_mg_prolong2 whose level-(l+2) correction rows u'' come from a third stage in registers instead of memory: every
+// lane holds x'' and u'' of the level-(l+2) column left of (or under) its coarse columns — in fp64 two lanes hold the
+// same one — with its neighbours SH2 lanes away; u'' and u' are never stored.  The stage advances one row per four
+// fine rows.  Same per-node expressions and order as fea_mg_prolong_sweep(u = NULL) on level l+2 followed by
+// fea_mg_prolong2 on level l (bitwise: tests/test_gpu_three_level.py).
+// Exact lanes: x'' everywhere, u'' on SH2 .. 63 - SH2, x' (u'' of its own lane and of the one SH2 to the right) on
+// SH2 .. 63 - 2 SH2, u' one lane in from both, x (the left lane's u') one more from the left, out one more from both.
+// ---------------------------------------------------------------------------
+template <typename T>
+struct OvlP3 {
+  static constexpr int V = Frame<T>::VEC;
+  static constexpr int SH2 = V == 2 ? 2 : 1;                  // lanes between two columns of level l+2
+  static constexpr int LO = SH2 + 3, HI = 63 - 2 * SH2 - 2;  // owning lanes (fp64 5 .. 57, fp32 4 .. 59)
+  static constexpr int S = (HI - LO + 1) * V;                // owned fine columns per strip (fp64 106, fp32 224)
+  static_assert(LO * V - 1 <= Frame<T>::OFF, "the left halo fits the frame");
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_mg_prolong3(Mg3Args<T> a) {
+  using F = Frame<T>;
+  using O = OvlP3<T>;
+  constexpr int V = F::VEC;
+  constexpr int Q = V / 2;
+  constexpr int SH2 = O::SH2;
+  const MgArgs<T>& g = a.g;
+  const TaskId id = decode_task_lin(g.nstrips, g.ntr);
+  if (!id.valid) return;
+  const int lane = lane_id();
+  const int H = g.H, Hc = g.Hc, W = g.W, Wc = g.Wc, Hc2 = g.Hc2, Wc2 = g.Wc2, Hc3 = a.Hc3, Wc3 = a.Wc3;
+  const int c0 = 1 + id.s * O::S;  // first owned fine column
+  const int cs = c0 - O::LO * V;   // first loaded column (odd)
+  const int cl = cs + V * lane;
+  const int r0 = 1 + id.t * g.rb;  // odd; g.rb is a multiple of 4, so (r0 - 1) / 2 is even
+  const int r1 = min(r0 + g.rb, H - 1);
+  T ks[9], ps[9];
+#pragma unroll
+  for (int d = 0; d < 9; ++d) {
+    ks[d] = g.ktab[d];
+    ps[d] = g.ptab[d];
+  }
+  const T om = g.omd[0];
+  const T w1 = g.w;
+  const int ld = g.ld, ldc = g.ldc, ldc2 = g.ldc2, ldc3 = a.ldc3;
+  bool cin[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) cin[k] = cl + k >= 1 && cl + k <= W - 2;
+  const bool own = lane >= O::LO && lane <= O::HI;
+  const int ll = min(lane, (W - 1 - cs) / V);  // lanes past the grid re-read the last needed line
+  const long long boff = (long long)id.b * g.bs + F::OFF + cs;
+  const T* __restrict__ fb = g.f + boff;
+  T* __restrict__ ob = g.out + boff;
+  // the lane's columns of the coarser levels (as the grid counts them, past its edges too: the masks below zero what
+  // lies outside; the loads stay inside the rows)
+  const int jc = (cs + 1) / 2;
+  const int J0 = jc + Q * lane;  // first column of level l+1
+  const int KL = (J0 - 1) >> 1;  // column of level l+2: KL and KL + 1 feed the lane's columns of level l+1
+  bool jin[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) jin[q] = J0 + q >= 1 && J0 + q <= Wc - 2;
+  const bool kin = KL >= 1 && KL <= Wc2 - 2;
+  const T* __restrict__ f2b = g.ec + (long long)id.b * g.bsc + F::OFF + jc + Q * ll;                    // f_{l+1}
+  const T* __restrict__ f3b = g.ec2 + (long long)id.b * g.bsc2 + F::OFF + min(max(KL, 0), Wc2 - 1);    // f_{l+2}
+  // level l+3 columns NL, NL + 1 feed column KL (odd KL: (KL-1)/2, (KL+1)/2; even KL: KL/2).  NL = -1 (in the frame)
+  // is kept for the boundary column KL = 0, whose x'' must come out as the 0 the level's left neighbour reads
+  const T* __restrict__ e4b = a.ec3 + (long long)id.b * a.bsc3 + F::OFF + min(max((KL - 1) >> 1, -1), Wc3 - 2);
+  auto rowo = [&](int r) -> long long { return (long long)(min(max(r, -1), H) + 1) * ld + V * ll; };
+  auto crowo = [&](int r) -> long long { return (long long)(min(max(r, -1), Hc) + 1) * ldc; };
+  auto c2rowo = [&](int r) -> long long { return (long long)(min(max(r, -1), Hc2) + 1) * ldc2; };
+  auto c3rowo = [&](int r) -> long long { return (long long)(min(max(r, -1), Hc3) + 1) * ldc3; };
+  const PRow<1> np1{};
+  const PRow<Q> npq{};
+  const PRow<V> npv{};
+
+  // crow_term on two coarse values e[0], e[1] (columns c, c + 1 with c = (col - 1) >> 1) for column `col` of the
+  // level above them (k_mg_prolong2's term2)
+  auto pterm = [&](const T (&e)[2], int col, int ky) -> T {
+    if (col & 1) {
+      T t = ps[ky * 3 + 2] * e[0];
+      t += ps[ky * 3 + 0] * e[1];
+      return t;
+    }
+    return ps[ky * 3 + 1] * e[1];
+  };
+
+  // ---- stage 3 (level l+2): x'' and u'' rows on column KL ----
+  struct In3 {  // inputs of x'' row d: f_{l+2}, e_{l+3} rows d >> 1, (d >> 1) + 1 on columns NL, NL + 1
+    T f;
+    T e[2][2];
+  };
+  auto ld3 = [&](int d) {
+    In3 r;
+    r.f = f3b[c2rowo(d)];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const long long o = c3rowo((d >> 1) + h);
+      r.e[h][0] = e4b[o];
+      r.e[h][1] = e4b[o + 1];
+    }
+    return r;
+  };
+  struct X3 {
+    Row<T, 1> x;
+    T f;
+  };
+  auto mkx3 = [&](const In3& r, int d) {
+    const bool din = d >= 1 && d <= Hc2 - 2;
+    T x[1];
+    x[0] = (din && kin) ? om * r.f : T(0);
+    if (d & 1) {
+      const T t = pterm(r.e[0], KL, 2) + pterm(r.e[1], KL, 0);
+      x[0] += w1 * t;
+    } else {
+      x[0] += w1 * pterm(r.e[0], KL, 1);
+    }
+    X3 w;
+    w.x = own_row_sh<T, 1, SH2>(x);
+    w.f = r.f;
+    return w;
+  };
+  struct E2 {  // a u'' row as level l+1 reads it: columns KL and KL + 1
+    T e[2];
+  };
+  auto mku3 = [&](const X3& x0, const X3& x1, const X3& x2, int c) {
+    const bool cin3 = c >= 1 && c <= Hc2 - 2;
+    const T u = jacobi<T, 1, false>(x0.x, x1.x, x2.x, np1, np1, np1, 0, x1.f, ks, om, nullptr);
+    E2 r;
+    r.e[0] = (cin3 && kin) ? u : T(0);
+    r.e[1] = shlz<SH2>(r.e[0]);
+    return r;
+  };
+
+  // ---- stage 2 (level l+1): k_mg_prolong2's coarse stage, its correction rows from stage 3 ----
+  struct In2 {
+    T f[Q];
+  };
+  auto ld2 = [&](int b) {
+    In2 r;
+    vload<T, Q>(f2b + crowo(b), r.f);
+    return r;
+  };
+  struct X2 {
+    Row<T, Q> x;
+    T f[Q];
+  };
+  auto mkx2 = [&](const In2& r, int b, const E2& lo, const E2& hi) {  // lo, hi: u'' rows b >> 1, (b >> 1) + 1
+    const bool bin = b >= 1 && b <= Hc - 2;
+    T x[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) x[q] = (bin && jin[q]) ? om * r.f[q] : T(0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int Jq = J0 + q;
+      if (b & 1) {
+        const T t = pterm(lo.e, Jq, 2) + pterm(hi.e, Jq, 0);
+        x[q] += w1 * t;
+      } else {
+        x[q] += w1 * pterm(lo.e, Jq, 1);
+      }
+    }
+    X2 w;
+    w.x = own_row<T, Q>(x);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) w.f[q] = r.f[q];
+    return w;
+  };
+  auto mku2 = [&](const X2& a_, const X2& b_, const X2& c_, int r) {
+    const bool ain = r >= 1 && r <= Hc - 2;
+    T o[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const T u = jacobi<T, Q, false>(a_.x, b_.x, c_.x, npq, npq, npq, q, b_.f[q], ks, om, nullptr);
+      o[q] = (ain && jin[q]) ? u : T(0);
+    }
+    CRow<T, V> c{};
+#pragma unroll
+    for (int q = 0; q < Q; ++q) c.e[q + 1] = o[q];
+    c.e[0] = shr1z(o[Q - 1]);
+    return c;
+  };
+
+  // ---- stage 1 (level l): k_mg_prolong_zu_ovl ----
+  struct In {
+    T f[V];
+  };
+  struct XR {
+    Row<T, V> x;
+    T f[V];
+  };
+  auto ld_f = [&](int y) {
+    In r;
+    vload<T, V>(fb + rowo(y), r.f);
+    return r;
+  };
+  auto zero_iterate = [&](const In& r, int y, T (&x)[V]) {
+    const bool rin = y >= 1 && y <= H - 2;
+#pragma unroll
+    for (int k = 0; k < V; ++k) x[k] = (rin && cin[k]) ? om * r.f[k] : T(0);
+  };
+  auto finish_x = [&](const In& r, const T (&x)[V]) {
+    XR w;
+    w.x = own_row<T, V>(x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) w.f[k] = r.f[k];
+    return w;
+  };
+  auto row_even = [&](const In& r, int y, const CRow<T, V>& ca) {
+    T x[V];
+    zero_iterate(r, y, x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) x[k] += w1 * crow_term<T, V, false>(ca, k + 1, 1, ps, nullptr);
+    return finish_x(r, x);
+  };
+  auto row_odd = [&](const In& r, int y, const CRow<T, V>& ca, const CRow<T, V>& cb) {
+    T x[V];
+    zero_iterate(r, y, x);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      const T t = crow_term<T, V, false>(ca, k + 1, 2, ps, nullptr) + crow_term<T, V, false>(cb, k + 1, 0, ps, nullptr);
+      x[k] += w1 * t;
+    }
+    return finish_x(r, x);
+  };
+  auto emit = [&](int y, const XR& xa, const XR& xb, const XR& xc) {
+    T o[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      o[k] = jacobi<T, V, false>(xa.x, xb.x, xc.x, npv, npv, npv, k, xb.f[k], ks, om, nullptr);
+    }
+    if (own && y < r1) store_masked<T, V, false>(ob + rowo(y), o, cl, W);
+  };
+
+  // every load of the start first: x'' rows cq-2 .. cq+3, x' rows a0-1 .. a0+2, fine rows r0-1, r0 and the ring
+  const int a0 = (r0 - 1) / 2;  // even
+  const int cq = a0 / 2;
+  const In3 t0 = ld3(cq - 2), t1 = ld3(cq - 1), t2 = ld3(cq), t3 = ld3(cq + 1), t4 = ld3(cq + 2);
+  In3 n3 = ld3(cq + 3);
+  const In2 s0 = ld2(a0 - 1), s1 = ld2(a0), s2 = ld2(a0 + 1), s3 = ld2(a0 + 2);
+  const In f0 = ld_f(r0 - 1), f1 = ld_f(r0);
+  // iteration y (odd) emits fine rows y, y+1 from fine rows y+1, y+2 and the x' row (y+5)/2, in flight two iterations
+  // ahead (ring slots consumed in place); every second iteration also takes the next x'' row, one body ahead
+  struct Slot {
+    In u1, u2;
+    In2 c;
+  };
+  Slot ring[2];
+  auto fill = [&](Slot& sl, int y) {
+    sl.u1 = ld_f(y + 1);
+    sl.u2 = ld_f(y + 2);
+    sl.c = ld2((y + 5) / 2);
+  };
+  fill(ring[0], r0);
+  fill(ring[1], r0 + 2);
+  // u'' rows cq-1, cq, cq+1
+  X3 Ya = mkx3(t0, cq - 2), Yb = mkx3(t1, cq - 1), Yc = mkx3(t2, cq);
+  const E2 Um = mku3(Ya, Yb, Yc, cq - 1);
+  Ya = Yb, Yb = Yc, Yc = mkx3(t3, cq + 1);
+  E2 U0 = mku3(Ya, Yb, Yc, cq);
+  Ya = Yb, Yb = Yc, Yc = mkx3(t4, cq + 2);
+  E2 U1 = mku3(Ya, Yb, Yc, cq + 1);
+  // x' rows a0-1 .. a0+2 -> u' rows a0 (C0), a0+1 (C1)
+  X2 Xa = mkx2(s0, a0 - 1, Um, U0);
+  X2 Xb = mkx2(s1, a0, U0, U0);
+  X2 Xc2 = mkx2(s2, a0 + 1, U0, U1);
+  const CRow<T, V> C0 = mku2(Xa, Xb, Xc2, a0);
+  Xa = Xb, Xb = Xc2, Xc2 = mkx2(s3, a0 + 2, U1, U1);
+  CRow<T, V> C1 = mku2(Xa, Xb, Xc2, a0 + 1);
+  XR Xp = row_even(f0, r0 - 1, C0);
+  XR Xc = row_odd(f1, r0, C0, C1);
+  // entering the body of y = r0 + 4k: U0, U1 = u'' rows cq+k, cq+k+1; its first iteration's x' row (y+5)/2 is odd and
+  // reads u'' rows cq+k+1, cq+k+2 (the new one, from x'' row dn = cq+k+3), its second one's is even and reads cq+k+2.
+  // Rows past r1 (the last task) are computed from clamped loads and not stored.
+  auto iter = [&](int y, auto slot, int dn) {
+    constexpr int SL = decltype(slot)::value;
+    Slot& sl = ring[SL];
+    if constexpr (SL == 0) {
+      Ya = Yb, Yb = Yc, Yc = mkx3(n3, dn);
+      n3 = ld3(dn + 1);
+      U0 = U1;
+      U1 = mku3(Ya, Yb, Yc, dn - 1);
+    }
+    const XR Xn = row_even(sl.u1, y + 1, C1);  // row y+1 (even, coarse (y+1)/2 = C1)
+    emit(y, Xp, Xc, Xn);
+    Xa = Xb, Xb = Xc2;
+    if constexpr (SL == 0) Xc2 = mkx2(sl.c, (y + 5) / 2, U0, U1);
+    else Xc2 = mkx2(sl.c, (y + 5) / 2, U1, U1);
+    const CRow<T, V> C2 = mku2(Xa, Xb, Xc2, (y + 3) / 2);
+    const XR Xnn = row_odd(sl.u2, y + 2, C1, C2);  // row y+2 (odd, coarse (y+1)/2 and (y+3)/2)
+    emit(y + 1, Xc, Xn, Xnn);
+    Xp = Xn;
+    Xc = Xnn;
+    C1 = C2;
+    fill(sl, y + 4);
+  };
+  int dn = cq + 3;
+  for (int y = r0; y < r1; y += 4, ++dn) {
+    iter(y, std::integral_constant<int, 0>{}, dn);
+    iter(y + 2, std::integral_constant<int, 1>{}, dn);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Kernel F: cycle join — the post-smooth of V-cycle k and the pre-smooth + residual + restriction
 // of V-cycle k+1 on one level in ONE pass (temporal blocking across the cycle boundary):
 //   x = u + w1 P(ec)        (FEANet/multigrid.py:177-180, prolongation + correction)
@@ -2902,6 +3481,87 @@ static int prolong2(const T* fc, const T* ec2, const T* f, T* out, const uint8_t
   else k_mg_prolong2<T, false><<<grid, 256, 0, s>>>(g);
   return launch_status();
 }
+
+// Three-level kernels (the register-strip form of fea_mg_mid_down / fea_mg_mid_up, k = 3): `units` is the task height
+// in rows of level l+3 (zero_restrict3: 8 fine rows each) or in groups of 4 fine rows (prolong3); 0 picks it by the
+// two-level kernels' balanced rule, which on the launch-bound levels these kernels are for gives the minimum, 1.
+// Results do not depend on it.  One stencil pattern only.
+template <typename T>
+static bool mg_coarse3(Mg3Args<T>& a, int ldc2, long long bsc2, int ldc3, long long bsc3) {
+  MgArgs<T>& g = a.g;
+  if (!coarse_ok<T>(g.Hc, g.Wc, ldc2, bsc2)) return false;
+  mg_coarse2(g, ldc2, bsc2);
+  if (!coarse_ok<T>(g.Hc2, g.Wc2, ldc3, bsc3)) return false;
+  a.Hc3 = (g.Hc2 + 1) / 2; a.Wc3 = (g.Wc2 + 1) / 2; a.ldc3 = ldc3; a.bsc3 = bsc3;
+  return true;
+}
+
+template <typename T>
+static int zero_restrict3(const T* f, T* fc, T* fc2, T* fc3, const uint8_t* pid, const T* ktab, const T* omd, int ntab,
+                          const T* rtab, int nrtab, T w0, int B, int H, int W, int ld, long long bs, int ldc,
+                          long long bsc, int ldc2, long long bsc2, int ldc3, long long bsc3, int units, void* stream) {
+  if (!restrict_ok<T>(f, fc, pid, ktab, ntab, rtab, nrtab, B, H, W, ld, bs, ldc, bsc) || !fc2 || !fc3 || !omd ||
+      ntab != 1 || units < 0)
+    return FEA_EINVAL;
+  Mg3Args<T> a{};
+  MgArgs<T>& g = a.g;
+  g = mg_args<T>(H, W, ld, bs, B);
+  g.f = f; g.out = fc; g.out2 = fc2; a.out3 = fc3; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  g.rtab = rtab; g.nrtab = nrtab; g.w = w0;
+  mg_coarse(g, ldc, bsc);
+  if (!mg_coarse3(a, ldc2, bsc2, ldc3, bsc3)) return FEA_EINVAL;
+  g.nstrips = div_up(W - 2, OvlZ3<T>::S);
+  const int rows_u = a.Hc3 - 2;
+  const int u = units > 0 ? std::min(units, rows_u) : balanced_units(B, g.nstrips, rows_u, 8, 21, 1);
+  g.rb = 8 * u;
+  g.ntr = div_up(rows_u, u);
+  k_mg_zero_restrict3<T><<<mg_grid_lin(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(a);
+  return launch_status();
+}
+
+template <typename T>
+static int prolong3(const T* fc, const T* fc2, const T* ec3, const T* f, T* out, const uint8_t* pid, const T* ktab,
+                    const T* omd, int ntab, const T* ptab, int nptab, T w1, int B, int H, int W, int ld, long long bs,
+                    int ldc, long long bsc, int ldc2, long long bsc2, int ldc3, long long bsc3, int units,
+                    void* stream) {
+  if (!fc || !fc2 || !ec3 || !f || !out || !omd || !ptab || B <= 0 || !layout_ok<T>(H, W, ld, bs)) return FEA_EINVAL;
+  if (!coarse_ok<T>(H, W, ldc, bsc) || !tab_ok(ktab, ntab, pid) || !xtab_ok(nptab, ntab) || ntab != 1 || units < 0)
+    return FEA_EINVAL;
+  Mg3Args<T> a{};
+  MgArgs<T>& g = a.g;
+  g = mg_args<T>(H, W, ld, bs, B);
+  g.ec = fc; g.ec2 = fc2; a.ec3 = ec3; g.f = f; g.out = out; g.pid = pid; g.ktab = ktab; g.omd = omd; g.ntab = ntab;
+  g.ptab = ptab; g.nptab = nptab; g.w = w1;
+  mg_coarse(g, ldc, bsc);
+  if (!mg_coarse3(a, ldc2, bsc2, ldc3, bsc3)) return FEA_EINVAL;
+  g.nstrips = div_up(W - 2, OvlP3<T>::S);
+  const int rows_u = div_up(H - 2, 4);
+  const int u = units > 0 ? std::min(units, rows_u) : balanced_units(B, g.nstrips, rows_u, 4, 10, 1);
+  g.rb = 4 * u;
+  g.ntr = div_up(H - 2, g.rb);
+  k_mg_prolong3<T><<<mg_grid_lin(B, g.ntr, g.nstrips), 256, 0, (hipStream_t)stream>>>(a);
+  return launch_status();
+}
+
+// What fea_mg_mid_down / fea_mg_mid_up (mid_ops.hip) call for their register-strip form: C++ linkage, not exported.
+namespace fea {
+#define FEA_STRIP3(T)                                                                                                \
+  int strip_zero_restrict3(const T* f, T* fc, T* fc2, T* fc3, const T* ktab, const T* omd, int ntab, const T* rtab,  \
+                           int nrtab, T w0, int B, int H, int W, const int* ld, const long long* bs, int units,      \
+                           void* stream) {                                                                           \
+    return zero_restrict3<T>(f, fc, fc2, fc3, nullptr, ktab, omd, ntab, rtab, nrtab, w0, B, H, W, ld[0], bs[0],      \
+                             ld[1], bs[1], ld[2], bs[2], ld[3], bs[3], units, stream);                               \
+  }                                                                                                                  \
+  int strip_prolong3(const T* fc, const T* fc2, const T* ec3, const T* f, T* out, const T* ktab, const T* omd,       \
+                     int ntab, const T* ptab, int nptab, T w1, int B, int H, int W, const int* ld,                   \
+                     const long long* bs, int units, void* stream) {                                                 \
+    return prolong3<T>(fc, fc2, ec3, f, out, nullptr, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld[0], bs[0],       \
+                       ld[1], bs[1], ld[2], bs[2], ld[3], bs[3], units, stream);                                     \
+  }
+FEA_STRIP3(float)
+FEA_STRIP3(double)
+#undef FEA_STRIP3
+}  // namespace fea
 
 // The exported symbols: each only forwards to its template.
 #define FEA_MG_API(SUF, T)                                                                                           \

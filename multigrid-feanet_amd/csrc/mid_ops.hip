@@ -725,6 +725,34 @@ __global__ __launch_bounds__(kMidThreads) void k_mg_mid_up(MidArgs<T> a) {
 
 using namespace fea;
 
+// The register-strip form of both entry points (framed_ops.hip: k_mg_zero_restrict3 / k_mg_prolong3, no LDS, no
+// barrier): selected by TR = -u, TC = -1 — wave tasks u units tall (a unit: one row of the lowest level going down,
+// four rows of the top level going up) instead of an LDS tile — for k = 3 and one stencil pattern.
+namespace fea {
+#define FEA_STRIP3_DECL(T)                                                                                          \
+  int strip_zero_restrict3(const T* f, T* fc, T* fc2, T* fc3, const T* ktab, const T* omd, int ntab, const T* rtab, \
+                           int nrtab, T w0, int B, int H, int W, const int* ld, const long long* bs, int units,     \
+                           void* stream);                                                                           \
+  int strip_prolong3(const T* fc, const T* fc2, const T* ec3, const T* f, T* out, const T* ktab, const T* omd,      \
+                     int ntab, const T* ptab, int nptab, T w1, int B, int H, int W, const int* ld,                  \
+                     const long long* bs, int units, void* stream);
+FEA_STRIP3_DECL(float)
+FEA_STRIP3_DECL(double)
+#undef FEA_STRIP3_DECL
+}  // namespace fea
+static inline bool mid_strips(int TR, int TC) { return TR < 0 && TC == -1; }
+
+// the levels' pitches (fea_mg_layout) for the strip form, which checks sizes and layouts itself
+template <typename T>
+static bool strip_layouts(int H, int W, int (&ld)[4], long long (&bs)[4]) {
+  for (int j = 0; j < 4; ++j) {
+    if (fea_mg_layout(H, W, (int)sizeof(T), &ld[j], &bs[j]) != 0) return false;
+    H = (H + 1) / 2;
+    W = (W + 1) / 2;
+  }
+  return true;
+}
+
 template <typename T>
 static int mid_fill(MidArgs<T>& a, int k, int B, int H, int W, int TR, int TC) {
   if (k < 1 || k > kMidMaxK || B <= 0 || B > 65535 || TR < 1 || TC < 1) return FEA_EINVAL;
@@ -759,6 +787,14 @@ static int mid_down(const T* const* f, const uint8_t* const* pid, int k, int B, 
   if (GATHER && (!gsrc || Pr < 1 || Pc < 1 || gcr < 1 || gcc < 1 || H - 1 != Pr * gcr || W - 1 != Pc * gcc))
     return FEA_EINVAL;
   const bool multi = ntab > 1;
+  if (!GATHER && mid_strips(TR, TC)) {
+    int ld[4];
+    long long bs[4];
+    if (k != 3 || multi || B > 65535 || !strip_layouts<T>(H, W, ld, bs) || !f[0] || !f[1] || !f[2] || !f[3])
+      return FEA_EINVAL;
+    return strip_zero_restrict3(f[0], const_cast<T*>(f[1]), const_cast<T*>(f[2]), const_cast<T*>(f[3]), ktab, omd,
+                                ntab, rtab, nrtab, w0, B, H, W, ld, bs, -TR, stream);
+  }
   if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;
   if (mid_down_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;
   for (int j = 0; j <= k; ++j) {
@@ -790,6 +826,14 @@ static int mid_up(const T* const* f, const T* e, T* out, const uint8_t* const* p
   MidArgs<T> a = {};
   if (!f || !e || !out || !omd || !ptab || !tab_ok(ktab, ntab, pid) || !xtab_ok(nptab, ntab)) return FEA_EINVAL;
   const bool multi = ntab > 1;
+  if (mid_strips(TR, TC)) {
+    int ld[4];
+    long long bs[4];
+    if (k != 3 || multi || B > 65535 || !strip_layouts<T>(H, W, ld, bs) || !f[0] || !f[1] || !f[2] || e == out ||
+        f[0] == out || f[1] == out || f[2] == out)
+      return FEA_EINVAL;
+    return strip_prolong3(f[1], f[2], e, f[0], out, ktab, omd, ntab, ptab, nptab, w1, B, H, W, ld, bs, -TR, stream);
+  }
   if (mid_fill<T>(a, k, B, H, W, TR, TC)) return FEA_EINVAL;
   if (mid_up_lds(k, TR, TC, (int)sizeof(T), multi) > kMidLdsBytes) return FEA_EINVAL;
   for (int j = 0; j <= k; ++j) {

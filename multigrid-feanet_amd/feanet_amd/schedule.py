@@ -22,6 +22,10 @@ Steps:
   ("mid_up", a, k, csrc, dst, T)       the "omdf" prolong_sweep steps of levels a+k-1..a in one
                                        launch: u_a[dst] from u_{a+k}[csrc] (tile T of level a)
                                        (group_mid rewrites a schedule into these)
+  ("resid_restrict3", l)               the zero-guess resid_restrict steps of levels l, l+1, l+2 (the three right
+                                       above the coarse tail) in one register-strip launch (group_triples)
+  ("prolong_sweep3", l, csrc, dst)     the "omdf" prolong_sweep steps of levels l+2, l+1, l in one launch: u_l[dst]
+                                       from the tail's output u_{l+3}[csrc]
   ("coarse_tail_ext", l, dst)          the zero-guess restriction of level l, the coarse tail of levels
                                        l+1..L-1 and level l's recomputed-iterate prolongation + sweep in one
                                        launch (fea_mg_coarse_tail_ext; extend_tail rewrites into it)
@@ -292,6 +296,39 @@ def pair_prolongations(steps, can_pair, finest_first=True):
                     k += 1
         out.extend(paired)
         i = j
+    return out
+
+
+def group_triples(steps, can_down, can_up):
+    """Rewrite the three single-level zero-guess restrictions right above the coarse tail (levels l, l+1, l+2 with
+    ("coarse_tail", l+3, c) next) into one ("resid_restrict3", l) step where can_down(l) allows it, and the three
+    recomputed-iterate prolongations right after the tail (levels l+2, l+1, l, chained from the tail's output c) into
+    one ("prolong_sweep3", l, c, dst) step, dst the buffer of level l's new iterate (those of levels l+2 and l+1 are
+    never stored), where can_up(l) allows it: the register-strip form of fea_mg_mid_down / fea_mg_mid_up, bitwise the
+    launches they replace.  Only a run of an ODD number of such levels is touched: the rest of it then pairs up
+    (pair_restrictions / pair_prolongations, run after this), one launch fewer each way; an even run already pairs
+    up and is left alone.  Run after group_mid."""
+    zr = lambda st: st[0] == "resid_restrict" and st[2] is None and st[3] is None
+    ps = lambda st: st[0] == "prolong_sweep" and st[2] == OMDF
+    out = list(steps)
+    for i, st in enumerate(steps):
+        if st[0] != "coarse_tail":
+            continue
+        t, c = st[1], st[2]
+        lo = i  # steps[lo:i]: the run of zero-guess restrictions of levels .. t-1 ending at the tail
+        while lo > 0 and zr(steps[lo - 1]) and steps[lo - 1][1] == t - (i - lo) - 1:
+            lo -= 1
+        hi = i + 1  # steps[i+1:hi]: the run of prolongations of levels t-1 .. chained from the tail's output
+        src = c
+        while hi < len(steps) and ps(steps[hi]) and steps[hi][1] == t - (hi - i) and steps[hi][3] == src:
+            src = steps[hi][4]
+            hi += 1
+        nd, nu = i - lo, hi - i - 1
+        if nu >= 3 and nu % 2 == 1 and can_up(t - 3):
+            out[i + 1:i + 4] = [("prolong_sweep3", t - 3, c, steps[i + 3][4])]
+        if nd >= 3 and nd % 2 == 1 and can_down(t - 3):
+            out[i - 3:i] = [("resid_restrict3", t - 3)]
+        break  # a schedule has one coarse tail
     return out
 
 

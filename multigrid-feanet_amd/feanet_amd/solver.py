@@ -26,7 +26,7 @@ import torch
 
 from . import _lib, mesh_setup as ms, ops
 from .graphs import GraphCache
-from .schedule import (OMDF, _other, extend_tail, group_hmid, group_mid, hjac_schedule, pair_prolongations, pair_restrictions,
+from .schedule import (OMDF, _other, extend_tail, group_hmid, group_mid, group_triples, hjac_schedule, pair_prolongations, pair_restrictions,
                        vcycle_schedule)
 
 
@@ -164,6 +164,14 @@ class MultigridSolver:
     MID_MAX_REDUNDANCY = 3.0  # staged top-level region / owned nodes (down pass)
     HMID_NODES = 300000   # learned-smoother levels paired into the HJac two-level launches: <= 513^2 nodes
     HMID_MIN_TILES = 64   # workgroups an HJac two-level launch should give the CUs (one per CU: LDS)
+    THREE_LEVEL_UP = True     # the three launch-bound levels right above the coarse tail run as one launch going up /
+    THREE_LEVEL_DOWN = False  # going down (the register-strip form of fea_mg_mid_up / fea_mg_mid_down, k = 3), bitwise
+    #                           the launches they replace (_three_level_ok: which plans; needs mid and pair_levels).  One switch per direction: up wins, down loses — a
+    #                           minimum-height task of the down kernel streams 29 rows of its top level in one wave.
+    #                           Same-process vcycle(1000), us per cycle, off / down / up / both: metric 129.7 / 130.9 /
+    #                           127.9 / 128.6, C2 33.5 / 34.3 / 31.4 / 31.5 (profiles/r07_ab/three_level.txt)
+    STRIP2_COLUMNS = {8: 116, 4: 244}  # Ovl2<T>::S and FEA_BAL2_WAVES of csrc/framed_ops.hip (_three_level_ok)
+    BAL2_WAVES = 1024
     TAIL_MAX_N = 65       # the coarse tail (one LDS-resident launch) covers the levels of at most this many rows / columns
     TAIL_EXT = True       # the single-level restriction / prolongation right above the coarse tail run inside the
     TAIL_EXT_MIN_BATCH = 64  # tail's launch (fea_mg_coarse_tail_ext: single pattern, V(1,1)) for batches of at least
@@ -482,11 +490,28 @@ class MultigridSolver:
             if self.mid:
                 steps = group_mid(steps, lambda lv: self._pick_mid(lv, False), lambda lv: self._pick_mid(lv, True))
             if self.pair_levels:
+                if self.mid:
+                    steps = group_triples(steps, lambda l: self.THREE_LEVEL_DOWN and self._three_level_ok(l),
+                                          lambda l: self.THREE_LEVEL_UP and self._three_level_ok(l))
                 ok = lambda l: l + 2 < self.L and self.levels[l + 2].H >= 3 and self.levels[l + 2].W >= 3
                 steps = pair_prolongations(pair_restrictions(steps, ok), ok)
             if self._tail_ext_ok():
                 steps = extend_tail(steps)
         return [self.bind_step(st) for st in steps], end
+
+    def _three_level_ok(self, l):
+        """Levels l, l+1, l+2 may run as one register-strip launch each way (fea_mg_mid_down / fea_mg_mid_up with
+        TR = TC = -1): the single-pattern Jacobi V(1,1) cycle from a stored finest iterate, level l+3 the coarse tail's
+        first, all three levels launch-bound and the tail not extended over level l+2.  Launch-bound: even at the
+        minimum task height (one row of level l+2 per wave task) the top level's two-level restriction has fewer waves
+        than the floor the two-level kernels keep — Ovl2::S owned columns per strip and FEA_BAL2_WAVES of
+        csrc/framed_ops.hip; at batch 1 levels of at most 513^2."""
+        top = self.levels[l]
+        strips = -(-(top.W - 2) // self.STRIP2_COLUMNS[top.esz])
+        launch_bound = self.B * strips * max(((top.H + 1) // 2 + 1) // 2 - 2, 1) < self.BAL2_WAVES
+        return (self.smoother == "jac" and self.ntab == 1 and self.nu1 == 1 and self.nu2 == 1 and self.compat is None
+                and not self.zero_start and self.tail_from is not None and l >= 1 and l + 3 == self.tail_from
+                and not self._tail_ext_ok() and launch_bound)
 
     def _tail_ext_ok(self):
         """fea_mg_coarse_tail_ext's scope: the single-pattern V(1,1) tail, the level above it at most 129 wide."""
@@ -631,6 +656,12 @@ class MultigridSolver:
         if kind == "resid_restrict2":
             return launch("mg_zero_restrict2", f=f, fc=lv[l + 1].f.data_ptr(), fc2=lv[l + 2].f.data_ptr(),
                           pidc=pid(l + 1), **sten(pid(l)), **rest(), **geom(l), **cp(l), **cp2(l))
+        if kind == "resid_restrict3":  # the register-strip form: TR = -1 (unit-height tasks), TC = -1
+            return launch("mg_mid_down", f=fs(l, 4), k=3, B=self.B, H=lv[l].H, W=lv[l].W, **sten(pids(l, 4)),
+                          **rest(), TR=-1, TC=-1)
+        if kind == "prolong_sweep3":
+            return launch("mg_mid_up", f=fs(l, 3), e=ptr(l + 3, st[2]), out=ptr(l, st[3]), k=3, B=self.B, H=lv[l].H,
+                          W=lv[l].W, **sten(pids(l, 4)), **prol(), TR=-1, TC=-1)
         if kind == "sweep_restrict":
             return launch("mg_sweep_restrict", u=ptr(l, st[2]), f=f, u_out=ptr(l, st[3]), fc=lv[l + 1].f.data_ptr(),
                           **sten(pid(l)), **rest(), **geom(l), **cp(l), norm_ws=None, norm_hist=None, norm_cnt=None)
