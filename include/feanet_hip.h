@@ -458,9 +458,11 @@ int fea_mg_prolong_hsweep_f64(const double* u, const double* u_raw, const double
                               int nlayers, const double* ptab, int nptab, double w1, int B, int H, int W, int ld,
                               long long bstride, int ldc, long long bstridec, void* stream);
 
-/* The whole coarse end of the V-cycle (levels t..t+nlev-1 of an Ht x Wt level, Ht, Wt <= 65 and
- * (Ht-1), (Wt-1) divisible by 2^(nlev-1)) in ONE launch,
- * one 1024-thread workgroup per sample, every level resident in LDS.  Input f_t and output v_t
+/* The whole coarse end of the V-cycle (levels t..t+nlev-1 of an Ht x Wt level) in ONE launch,
+ * one 1024-thread workgroup per sample, every level resident in LDS.  Dimension rule (the same for
+ * fea_mg_coarse_tail_ext's tail, Ht = (Hx+1)/2 and Wt = (Wx+1)/2, and for fea_mg_hjac_tail): 3 <= Ht, Wt <= 65,
+ * Ht and Wt independent, (Ht-1) and (Wt-1) divisible by 2^(nlev-1) and every level at least 3 nodes each way, so
+ * the node counts need not be 2^k + 1 and the coarsest level's may be even (97 -> 49, 25, 13, 7, 4).  Input f_t and output v_t
  * are framed level-t buffers (ld_t, bs_t); v_t's interior is written.  The sub-cycle starts from a
  * zero guess: nu1 pre-sweeps per level (none if q2), nu1+nu2 (q2: nu2) sweeps on the coarsest,
  * prolongation + correction + nu2 post-sweeps (FEANet/multigrid.py:165-183 below level t).
@@ -489,8 +491,8 @@ int fea_mg_coarse_tail_ext_f64(const double* f_x, double* v_x, int Hx, int Wx, i
 size_t fea_mg_coarse_tail_lds_bytes(int Ht, int Wt, int nlev, int elem_size, int multi);
 
 /* The coarse end of the learned-smoother V-cycle (MultiGrid.Step mode='hjac', M-FEANet-mg_test.ipynb:27346-27372
- * with Relax = HJacIterator.HRelax :147-155) for levels t..t+nlev-1 of an Ht x Wt level (Ht, Wt <= 65) in ONE
- * launch, one 1024-thread workgroup per sample, every level resident in LDS (hjac_tail.hip).  From a zero guess:
+ * with Relax = HJacIterator.HRelax :147-155) for levels t..t+nlev-1 of an Ht x Wt level (the coarse tail's
+ * dimension rule) in ONE launch, one 1024-thread workgroup per sample, every level resident in LDS (hjac_tail.hip).  From a zero guess:
  * nu1 HRelax pre-sweeps per level, residual + restriction, nu1+nu2 sweeps on the coarsest, prolongation +
  * correction + nu2 post-sweeps; hw = nlayers 3x3 HNet weights.  Bitwise the per-level fea_mg_hsweep /
  * fea_mg_residual_restrict / fea_mg_prolong_add sequence it replaces (feanet_amd.schedule.hjac_schedule).

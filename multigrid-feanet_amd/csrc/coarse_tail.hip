@@ -92,7 +92,10 @@ __device__ __forceinline__ int tail_off(int Ht, int Wt, int k) {  // element off
 //             iterate recomputed, as the streaming kernels do), v' = x + omd (f - K x) -> barrier
 //             (level 0: v' goes straight to HBM)
 // Every node value is the same expression, in the same order, as the general path (bitwise):
-// acc chains start from 0 and add the taps in (row, column) order; x = fma(w1, P e, omd f).
+// acc chains start from 0 and add the taps in (row, column) order; x = fma(w1, P e, omd f) with P e summed as the
+// streaming kernels do (crow_term of framed_ops.hip: per coarse row, an odd column's left coarse node first; an odd
+// row's two coarse rows as two terms) — so a V(1,1) cycle with the tail is bitwise the cycle with one launch per
+// level op (tests/test_gpu_odd_grids.py::test_solver_96_tail_on_off_bitwise).
 // ---------------------------------------------------------------------------------------------
 constexpr int kTailDownRows = (31 + kTailThreads / 64 - 1) / (kTailThreads / 64);  // coarse rows per wave going down:
 //                                                                                   Hc - 2 <= 31 (2 over 16 waves)
@@ -339,17 +342,22 @@ struct TailFast {
     }
     T x[R], xl[R], xr[R];
     int ql[R], qr[R];
+    // coarse row c's contribution with row tap ky: crow_term of framed_ops.hip (odd column: the left coarse node,
+    // kx = 2, then the right one, kx = 0), so the level is bitwise fea_mg_prolong_sweep(u = NULL)
+    auto crow = [&](int c, int ky) -> T {
+      T t = pw(pb[c], ky * 3 + 2) * eb[c];
+      t += pw(pa[c], ky * 3 + 0) * ea[c];
+      const T te = pw(pa[c], ky * 3 + 1) * ea[c];
+      return odd ? t : te;
+    };
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      T acc = 0;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        if ((PAR + j + 1 - ky) & 1) continue;  // coarse row (y + 1 - ky) / 2 exists only for even y + 1 - ky
-        const int c = (PAR + j + 1 - ky) >> 1;
-        const T cfa = odd ? pw(pa[c], ky * 3 + 0) : pw(pa[c], ky * 3 + 1);
-        const T t = acc + cfa * ea[c];
-        const T t2 = t + pw(pb[c], ky * 3 + 2) * eb[c];
-        acc = odd ? t2 : t;
+      T acc;
+      if ((PAR + j) & 1) {  // odd row y: coarse rows (y - 1) / 2 (ky = 2) and (y + 1) / 2 (ky = 0), summed as two terms
+        const T ta = crow((PAR + j - 1) >> 1, 2), tb = crow((PAR + j + 1) >> 1, 0);
+        acc = ta + tb;
+      } else {  // even row: coarse row y / 2, ky = 1
+        acc = crow((PAR + j) >> 1, 1);
       }
       const T v0 = omega(q[j]) * fr[j];
       const T xv = keep(v0 + a.w1 * acc);
@@ -587,20 +595,25 @@ __global__ __launch_bounds__(kTailThreads) void k_mg_coarse_tail(TailArgs<T> a) 
   };
   auto prolong_add = [&](int H, int N, const uint8_t* pkc, T* v, const T* e) {  // v += w1 P e, interior
     const int Nc = (N + 1) / 2;
+    // coarse row cy's contribution at fine column x with row tap ky (crow_term of framed_ops.hip)
+    auto crow = [&](int cy, int ky, int x) -> T {
+      if (!(x & 1)) {
+        const int j = cy * Nc + (x >> 1);
+        return ptb[P(pkc, j) + ky * 3 + 1] * e[j];
+      }
+      const int j = cy * Nc + ((x - 1) >> 1);
+      T t = ptb[P(pkc, j) + ky * 3 + 2] * e[j];
+      t += ptb[P(pkc, j + 1) + ky * 3 + 0] * e[j + 1];
+      return t;
+    };
     for (int y = 1 + ty; y <= H - 2; y += kTy)
       for (int x = 1 + tx; x <= N - 2; x += 32) {
-      T acc = 0;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        const int cy = y + 1 - ky;
-        if (cy & 1) continue;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const int cx = x + 1 - kx;
-          if (cx & 1) continue;
-          const int j = (cy >> 1) * Nc + (cx >> 1);
-          acc += ptb[P(pkc, j) + ky * 3 + kx] * e[j];
-        }
+      T acc;
+      if (y & 1) {
+        const T ta = crow((y - 1) >> 1, 2, x), tb = crow((y + 1) >> 1, 0, x);
+        acc = ta + tb;
+      } else {
+        acc = crow(y >> 1, 1, x);
       }
       v[y * N + x] += a.w1 * acc;
     }

@@ -111,9 +111,11 @@ class MultigridSolver:
     """Geometric-multigrid V-cycle for FEANet's structured-quad FE problems on one MI355X.
 
     Args:
-        n: fine-grid intervals per edge (N = n + 1 nodes), a power of two >= 2.
-        rows: intervals in the row direction when the domain is a rectangle (Poisson, or the two-material
-            problem with explicit pid_maps; default n, the reference's square).  n and rows must be divisible by 2^(L-1).
+        n: fine-grid intervals per edge (N = n + 1 nodes).  A power of two >= 2 when `rows` is omitted (the
+            reference's square); with `rows` given, any n and rows divisible by 2^(L-1) that leave at least 2
+            intervals each way on the coarsest level, e.g. MultigridSolver(96, rows=96): 97, 49, 25, 13, 7, 4 nodes.
+        rows: intervals in the row direction: a rectangle (Poisson, or the two-material problem with explicit
+            pid_maps), or rows = n for a square whose n is not a power of two (default n).
         levels: number of levels L (default int(log2 n), the reference's choice; coarsest n/2^(L-1);
             for a rectangle, the most levels whose coarsest grid has >= 2 intervals each way).
         problem: "poisson" (MeshSquare, one stencil) or "interface" (MeshCenterInterface, 16

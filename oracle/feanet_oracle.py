@@ -298,7 +298,9 @@ def hnet(x, geo, weights):
 # ---------------------------------------------------------------------------
 class Level:
     """pids: optional {N: pattern map} of the two-material problem computed earlier by interface_mesh (the
-    element/node loops are O(N^2) Python: tests/golden/c3_pattern_maps.npz holds their output up to 2049^2)."""
+    element/node loops are O(N^2) Python: tests/golden/c3_pattern_maps.npz holds their output up to 2049^2).
+    A key (H, W) gives the map of an H x W level instead: a window of a square's map (a rectangle, or a square cut
+    off centre), the only way the two-material problem gets a grid that is not the whole square."""
 
     def __init__(self, n, problem="poisson", dtype=np.float32, prop=(1, 20), shape=0, omega=2. / 3., m=None,
                  pids=None):
@@ -309,6 +311,11 @@ class Level:
         self.dtype = dtype
         if problem == "poisson":
             self.ktab, self.pid = square_mesh((self.H, self.W))
+        elif pids is not None and (self.H, self.W) in pids:
+            a = np.array(prop, np.float32)
+            self.ktab = np.stack([pattern_stencil(a, REF_PATTERNS[k]) for k in range(16)])
+            self.pid = np.asarray(pids[(self.H, self.W)], np.uint8)
+            assert self.pid.shape == (self.H, self.W)
         elif pids is not None and self.N in pids:
             assert self.m == n, "two-material problem: square only"
             a = np.array(prop, np.float32)

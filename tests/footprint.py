@@ -820,9 +820,13 @@ DESC = {
     "mg_hsweep": Desc(_hsweep, SINGLE, ("", "zero", "raw", "one layer")),
     "mg_hsweep_restrict": Desc(_hsweep, ONE, ("", "zero", "raw")),
     "mg_prolong_hsweep": Desc(_hsweep, ONE, ("", "raw")),
-    "mg_coarse_tail": Desc(_tail, [((5, 5, 2), "nlev 2"), ((17, 65, 2), "nlev 3"), ((17, 65, 2), "nlev 4")]),
-    "mg_coarse_tail_ext": Desc(_tail, [((9, 17, 2), "nlev 2"), ((33, 129, 2), "nlev 3")], two=False),
-    "mg_hjac_tail": Desc(_tail, [((5, 5, 2), "nlev 2"), ((17, 65, 2), "nlev 3"), ((17, 65, 2), "nlev 4")]),
+    # (49 x 25, four levels down to 7 x 4, and 97 x 49 above it: three rows per wave, an even coarsest level)
+    "mg_coarse_tail": Desc(_tail, [((5, 5, 2), "nlev 2"), ((17, 65, 2), "nlev 3"), ((17, 65, 2), "nlev 4"),
+                                   ((49, 25, 2), "nlev 4")]),
+    "mg_coarse_tail_ext": Desc(_tail, [((9, 17, 2), "nlev 2"), ((33, 129, 2), "nlev 3"), ((97, 49, 2), "nlev 4")],
+                               two=False),
+    "mg_hjac_tail": Desc(_tail, [((5, 5, 2), "nlev 2"), ((17, 65, 2), "nlev 3"), ((17, 65, 2), "nlev 4"),
+                                 ((49, 25, 2), "nlev 4")]),
     "mg_mid_down": Desc(_mid, MID_DOWN),
     "mg_mid_down_gathered": Desc(_mid, MID_DOWN),
     "mg_mid_up": Desc(_mid, MID_UP),

@@ -353,18 +353,21 @@ def test_hjac_fused_schedule_bitwise(T, problem, n, B, nu):
 @pytest.mark.parametrize("problem,m,n,B,nl,nu", [("poisson", 512, 512, 1, 3, (1, 1)), ("poisson", 1024, 1024, 2, 3, (1, 1)),
                                                  ("poisson", 256, 512, 1, 2, (1, 1)), ("poisson", 512, 512, 1, 1, (2, 1)),
                                                  ("poisson", 512, 512, 2, 3, (1, 2)), ("interface", 512, 512, 1, 3, (1, 1)),
-                                                 ("interface", 512, 512, 2, 2, (1, 1))])
+                                                 ("interface", 512, 512, 2, 2, (1, 1)),
+                                                 ("poisson", 96, 192, 1, 3, (1, 1)), ("poisson", 192, 192, 2, 3, (1, 1))])
 @pytest.mark.parametrize("tiles", ["default", "largest", "smallest"])
 def test_hjac_hmid_bitwise(T, problem, m, n, B, nl, nu, tiles):
     """fea_mg_hmid_down / fea_mg_hmid_up (two HJac levels per launch, hmid_ops.hip) are bitwise the fused per-level
     kernels they replace (mid=False): whole V-cycles, both problems, batches, 1-3 HNet layers, rows != columns,
-    V(2,1) / V(1,2) (only the up / down pairs apply), every tile size the solver may pick."""
+    V(2,1) / V(1,2) (only the up / down pairs apply), every tile size the solver may pick.  The grids of 193 columns
+    run without the HJac tail: with it only level 1 streams and nothing pairs; without it the pairs are
+    49 / 25 (-> 13) and 13 / 7 (-> 4) nodes a side, on 97 x 193 nodes 49 x 97 / 25 x 49 and 13 x 25 / 7 x 13."""
     from feanet_amd.solver import MultigridSolver
     rng = np.random.default_rng(m + n + B + nl)
     hw = (0.25 * rng.standard_normal((nl, 3, 3))).astype(np.float32)
     f = torch.from_numpy(rng.standard_normal((B, 1, m + 1, n + 1))).to("cuda", T)
     kw = dict(dtype=T, batch=B, smoother="hjac", hnet=hw, problem=problem, nu1=nu[0], nu2=nu[1],
-              rows=None if m == n else m)
+              rows=None if m == n and n != 192 else m, coarse_tail=n != 192)
     out = []
     for mid in (True, False):
         s = MultigridSolver(n, mid=mid, **kw)
@@ -415,7 +418,8 @@ def test_hmid_api_rejects_bad_arguments():
 
 
 @pytest.mark.parametrize("T", [torch.float32, torch.float64])
-@pytest.mark.parametrize("problem,m,n,B", [("poisson", 256, 256, 2), ("poisson", 128, 512, 1), ("interface", 256, 256, 1)])
+@pytest.mark.parametrize("problem,m,n,B", [("poisson", 256, 256, 2), ("poisson", 128, 512, 1), ("interface", 256, 256, 1),
+                                           ("poisson", 96, 192, 1), ("poisson", 192, 192, 2)])
 @pytest.mark.parametrize("nl", [0, 1, 2, 3])
 def test_hmid_kernels_vs_per_level_calls(T, problem, m, n, B, nl):
     """The C-ABI of the HJac two-level launches against the per-level calls they replace, every HNet depth the ABI

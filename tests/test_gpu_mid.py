@@ -31,6 +31,9 @@ def pid_arr(lv, problem):
 CASES = [  # (n, m, k, down tile, up tile); a region row must fit one wave (<= 64 columns)
     (64, 64, 2, 4, 16), (64, 64, 3, 2, 8), (128, 128, 3, 4, 32), (128, 64, 2, 8, 62), (256, 256, 4, 1, 24),
     (256, 128, 3, 5, 7), (512, 512, 3, 4, 32), (32, 32, 1, 3, 5), (1024, 1024, 3, 4, 62),
+    # levels that are not 2^k + 1: 97 -> 13, 193 x 97 -> 13 x 7 (k = 4: a down tile of 1 is the only one whose
+    # region row fits a wave), 81 x 113 -> 11 x 15, 49 -> 7
+    (96, 96, 3, 4, 16), (192, 96, 4, 1, 8), (80, 112, 3, 5, 7), (48, 48, 3, 3, 5),
 ]
 
 

@@ -11,8 +11,10 @@ pytestmark = pytest.mark.gpu
 
 # (columns n, rows m, batch): 16 is the smallest grid with three coarser levels (17 -> 9 -> 5 -> 3); rows != columns
 # both ways; 512 columns are five fp64 strips (104 owned columns each) and three fp32 ones (224); 488 x 120 ends its
-# last strip a few columns past an owned boundary and its lowest level has an even number of nodes (62 x 16)
-SHAPES = [(16, 16, 1), (16, 16, 3), (32, 32, 3), (64, 64, 1), (256, 32, 1), (32, 256, 3), (512, 32, 1), (488, 120, 1)]
+# last strip a few columns past an owned boundary and its lowest level has an even number of nodes (62 x 16);
+# 384 x 96 both ways: 385 / 193 / 97 columns over 97 / 49 / 25 rows, the levels MultigridSolver(768, rows=768) groups
+SHAPES = [(16, 16, 1), (16, 16, 3), (32, 32, 3), (64, 64, 1), (256, 32, 1), (32, 256, 3), (512, 32, 1), (488, 120, 1),
+          (384, 96, 1), (96, 384, 3)]
 
 
 def heights(rows_u):
