@@ -7,6 +7,8 @@ replay.  That state machine and the capture mechanics (a side stream, joined wit
 after, torch's capture_error_mode) live here, once; the callers pass a callable that issues the work, so a replay
 builds no launch list.
 """
+import gc
+
 import torch
 
 
@@ -25,6 +27,13 @@ class StreamCapture:
         g = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(stream)
+        # No cyclic garbage collection inside the capture.  A dead solver that sits in a reference cycle (a DDSolver
+        # does) keeps its captured graphs until the collector finds it; found during a capture, its graphs are
+        # destroyed while a stream captures, which HIP refuses ("operation not permitted when stream is
+        # capturing") — inside ~CUDAGraph, so the process aborts.  torch collects ahead of a capture only under
+        # torch.compiler.config.force_cudagraph_gc.
+        collecting = gc.isenabled()
+        gc.disable()
         try:
             with torch.cuda.graph(g, stream=side, **self.kw):
                 issue()
@@ -32,6 +41,9 @@ class StreamCapture:
             torch.cuda.synchronize(self.device)
             stream.wait_stream(side)
             raise
+        finally:
+            if collecting:
+                gc.enable()
         stream.wait_stream(side)
         return g
 

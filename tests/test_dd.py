@@ -276,3 +276,121 @@ def test_rect_records_decompose_the_dd_copies():
     assert r2.shape == (1, 6) and list(r2[0, 2:]) == [50, 50, B, 20]
     assert _rect_records(field[:, 1:4, 0:1].transpose(1, 2), field[:, 1:4, 2:3].transpose(1, 2)) is None
 
+
+
+def _framed(B, H, W, dtype):
+    """A framed buffer (as MultigridSolver's levels hold them) on the host whose every element is its own flat index,
+    and its layout (footprint.Geo)."""
+    import torch
+    import footprint as fp
+    geo = fp.Geo(H, W, B, torch.empty(0, dtype=dtype).element_size())
+    assert geo.numel < 1 << 24  # (exact in fp32 too)
+    return torch.arange(geo.numel, dtype=dtype), geo
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_block_and_rows_views_name_the_frame_nodes(dtype):
+    """dd._block / dd._rows (every halo region, gather source and scatter view of the decomposed solver): element
+    [b, y, x] of the view is node (y0 + y, x0 + x) of sample b as the framed layout places it — column 0 of a row
+    128 bytes minus one element into it, whatever the element size (tests/footprint.py's Geo.index, which the
+    kernels' write-footprint tests are built on)."""
+    import torch
+    from feanet_amd.dd import _block, _rows
+    dtype = getattr(torch, dtype)
+    B, H, W = 2, 11, 21
+    t, geo = _framed(B, H, W, dtype)
+    for y0, y1, x0, x1 in [(0, H, 0, W), (3, 7, 2, 5), (1, 2, W - 1, W), (H - 3, H, 0, 3)]:
+        v = _block(t, B, geo.bs, geo.ld, y0, y1, x0, x1)
+        want = torch.from_numpy(geo.index(np.arange(y0, y1), np.arange(x0, x1)))
+        assert v.shape == want.shape and torch.equal(v.to(torch.int64), want), (y0, y1, x0, x1)
+    for y0, y1 in [(0, H), (3, 5), (H - 1, H)]:
+        v = _rows(t, B, geo.bs, geo.ld, y0, y1)
+        assert v.shape == (B, (y1 - y0) * geo.ld) and v.is_contiguous() == (B == 1)
+        nodes = v.reshape(B, y1 - y0, geo.ld)[:, :, geo.off:geo.off + W]  # whole framed rows: the nodes sit at off
+        want = torch.from_numpy(geo.index(np.arange(y0, y1), np.arange(W)))
+        assert torch.equal(nodes.to(torch.int64), want), (y0, y1)
+        assert int(v[0, 0]) == int(want[0, 0, 0]) - geo.off  # and the run starts where the frame row does
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_staging_records(dtype):
+    """dd._Staging's block table (fea_dd_copy_blocks reads it) over [B, rows, cols] block views and [B, run] row
+    runs of two samples: one record per view and sample, in order; the frame address is the view's sample b, the
+    stage address the running element offset into the buffer, ld the view's row pitch (a run: one row of its own
+    length), the last word rows | cols << 32; the records tile the buffer without gaps.  Replayed with numpy, the
+    table packs the views in order and unpacks them again."""
+    import torch
+    from feanet_amd.dd import _block, _rows, _Staging
+    dtype = getattr(torch, dtype)
+    B, H, W = 2, 11, 21
+    t, geo = _framed(B, H, W, dtype)
+    views = [_block(t, B, geo.bs, geo.ld, 1, 4, 2, 7), _rows(t, B, geo.bs, geo.ld, 4, 6),
+             _block(t, B, geo.bs, geo.ld, 3, 10, W - 3, W), _block(t, B, geo.bs, geo.ld, 5, 6, 5, 6),
+             _rows(t, B, geo.bs, geo.ld, H - 1, H)]
+    st = _Staging(views, t.device, dtype)
+    esz = t.element_size()
+    assert st.esz == esz and st.buf.dtype == dtype and st.records.dtype == np.int64
+    assert st.records.shape == (len(views) * B, 4)
+    off, k = 0, 0
+    for v in views:
+        rows, cols = (1, v.shape[1]) if v.dim() == 2 else v.shape[1:]
+        for b in range(B):
+            base, stage, ld, word = (int(x) for x in st.records[k])
+            assert base == (v[b, 0] if v.dim() == 2 else v[b, 0, 0]).data_ptr(), k
+            assert stage == st.buf[off:].data_ptr(), k
+            assert ld == (cols if v.dim() == 2 else v.stride(1)), k
+            assert word == rows | (cols << 32) and (word & 0xFFFFFFFF, word >> 32) == (rows, cols), k
+            off += rows * cols
+            k += 1
+    assert off == st.n == sum(v.numel() for v in views) == st.buf.numel()  # no gap, nothing past the end
+    # the table replayed: pack, then unpack into a cleared frame
+    flat, stage = t.numpy(), st.buf.numpy()
+    stage[:] = -1
+
+    def replay(to_stage):
+        for base, sa, ld, word in st.records:
+            rows, cols = int(word) & 0xFFFFFFFF, int(word) >> 32
+            for r in range(rows):
+                f0, s0 = (int(base) - t.data_ptr()) // esz + r * int(ld), (int(sa) - st.buf.data_ptr()) // esz + r * cols
+                if to_stage:
+                    stage[s0:s0 + cols] = flat[f0:f0 + cols]
+                else:
+                    flat[f0:f0 + cols] = stage[s0:s0 + cols]
+    replay(True)
+    assert torch.equal(st.buf, torch.cat([v[b].reshape(-1) for v in views for b in range(B)]))
+    kept = [v.clone() for v in views]
+    t.zero_()
+    replay(False)
+    assert all(torch.equal(v, w) for v, w in zip(views, kept))
+    covered = torch.zeros_like(t, dtype=torch.bool)
+    for v in views:
+        torch.as_strided(covered, v.shape, v.stride(), v.storage_offset()).fill_(True)
+    assert not t[~covered].any()  # and nothing outside the views was written
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_halo_staging_segments(dtype):
+    """dd.halo_staging: the send views of all regions grouped per neighbour (peers ascending, a peer's views in item
+    order) in one staging buffer, the receive views likewise in another; each neighbour's message is one segment
+    (peer, element offset, element count), and the segments tile their buffer without gaps."""
+    import torch
+    from feanet_amd.dd import _block, halo_staging
+    dtype = getattr(torch, dtype)
+    B, H, W = 2, 11, 21
+    t, geo = _framed(B, H, W, dtype)
+    blk = lambda *a: _block(t, B, geo.bs, geo.ld, *a)
+    # (peer, direction, send view, receive view): two items' regions towards peers 3, 1 and 2, interleaved
+    regs = [(3, (1, 0), blk(7, 9, 1, 20), blk(9, 11, 1, 20)), (1, (0, -1), blk(1, 9, 1, 4), blk(1, 9, 0, 1)),
+            (2, (1, -1), blk(7, 9, 1, 3), blk(9, 10, 0, 1)), (3, (1, 0), blk(6, 9, 2, 19), blk(9, 10, 2, 19)),
+            (1, (0, -1), blk(2, 8, 1, 2), blk(2, 8, 0, 1))]
+    send, recv, seg_s, seg_r = halo_staging(regs)
+    assert [q for q, _, _ in seg_s] == [q for q, _, _ in seg_r] == [1, 2, 3]
+    for stg, segs, which in ((send, seg_s, 2), (recv, seg_r, 3)):
+        order = [r[which] for q in (1, 2, 3) for r in regs if r[0] == q]
+        assert [int(a) for a in stg.records[:, 0]] == [v[b, 0, 0].data_ptr() for v in order for b in range(B)]
+        at = 0
+        for q, o, cnt in segs:
+            assert o == at and cnt == sum(r[which].numel() for r in regs if r[0] == q)
+            at += cnt
+        assert at == stg.n == stg.buf.numel()
+        assert stg.buf.dtype == dtype

@@ -25,10 +25,12 @@ def _free_port():
 
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("ranks,grid,extra", [(2, None, []), (4, "2x2", []),
-                                              (4, "2x2", ["--problem", "interface", "--smoother", "hjac"])])
+                                              (4, "2x2", ["--problem", "interface", "--smoother", "hjac"]),
+                                              (2, None, ["--dtype", "f32"])])
 def test_bench_dd_line_parity(ranks, grid, extra):
     """The N > 1 line over gloo: every mode bitwise; also the decomposed two-material problem with the learned
-    smoother (--problem interface --smoother hjac)."""
+    smoother (--problem interface --smoother hjac), and the fp32 line (--dtype f32), whose dd_parity compares fp32
+    fields bitwise."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", str(ranks), "--full", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--global-n", "1024",
@@ -57,9 +59,10 @@ def test_bench_dd_line_parity(ranks, grid, extra):
     best = min(timed, key=lambda m: m["ms_per_step"])
     assert rec["headline_mode"] == best["mode"] and rec["ms_per_step"] == best["ms_per_step"]
     assert rec["config"]["dd_mode"]["mode"] == best["mode"]
-    if extra:
+    if "--problem" in extra:
         assert "interface" in rec["config"]["workload"] and "HRelax" in rec["config"]["workload"]
         assert base["workload"].startswith("1025x1025 interface")
+    assert rec["dtype"] == ("f32" if "f32" in extra else "f64")
 
 
 @pytest.mark.timeout(300)

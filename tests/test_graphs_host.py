@@ -117,3 +117,51 @@ def test_confirm_sees_the_capture_error():
     with pytest.raises(ValueError, match="decided elsewhere"):
         c.run("x", lambda: None, confirm=raising)
     assert len(c) == 0
+
+
+@pytest.mark.parametrize("fail", [False, True])
+def test_stream_capture_holds_the_cyclic_collector(monkeypatch, fail):
+    """StreamCapture runs issue() with Python's cyclic collector off and restores it, also when the capture raises:
+    a dead solver in a reference cycle owns captured graphs, and collecting it inside a capture destroys them while a
+    stream captures — HIP refuses that inside a destructor and the process aborts.  torch.cuda's pieces are stubs."""
+    import contextlib
+    import gc
+
+    import torch
+    from feanet_amd.graphs import StreamCapture
+
+    class Stream:
+        def __init__(self, device=None):
+            pass
+
+        def wait_stream(self, other):
+            pass
+
+    @contextlib.contextmanager
+    def graph(g, stream=None, **kw):
+        yield
+
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: Stream())
+    monkeypatch.setattr(torch.cuda, "Stream", Stream)
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", object)
+    monkeypatch.setattr(torch.cuda, "graph", graph)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda device=None: None)
+    seen = []
+
+    def issue():
+        seen.append(gc.isenabled())
+        if fail:
+            raise RuntimeError("operation not permitted when stream is capturing")
+    assert gc.isenabled()
+    if fail:
+        with pytest.raises(RuntimeError):
+            StreamCapture("cuda")(issue)
+    else:
+        assert StreamCapture("cuda")(issue) is not None
+    assert seen == [False] and gc.isenabled()
+    gc.disable()  # a caller that had it off keeps it off
+    try:
+        StreamCapture("cuda")(lambda: None)
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
