@@ -130,7 +130,15 @@ _EXTRA = {
     "fea_transfer_weight_grad_ws_bytes_f32": ("I C, I B, I Hc, I Wc", ctypes.c_size_t),
     "fea_transfer_weight_grad_ws_bytes_f64": ("I C, I B, I Hc, I Wc", ctypes.c_size_t),
 }
+# the full-multigrid transfers, declared in include/feanet_fmg.h (typed pairs, the field syntax of _SIGS;
+# tests/test_fmg_host.py compares this table with that header)
+_FMG = {
+    "fmg_prolong": "P u, P ec, P out, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, I order, P stream",
+    "fmg_restrict": "P f, P fc, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "fmg_boundary": "P bc, LL bc_bstride, I stride, P dst, I B, I H, I W, I ld, LL bstride, P stream",
+}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
+_FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
 _SIGS = {name: sig.split(", ") for name, sig in _SIGS.items()}
 _EXTRA = {name: (sig.split(", ") if sig else [], res) for name, (sig, res) in _EXTRA.items()}
 
@@ -147,7 +155,7 @@ _NAMES = {}  # launch name -> parameter names in C-ABI order, without the traili
 def _names(name):
     """Parameter names of a launch record's entry point: a typed pair's base name, or a dtype-free fea_<name>."""
     if name not in _NAMES:
-        sig = _SIGS.get(name) or _EXTRA.get("fea_" + name, ([],))[0]
+        sig = _SIGS.get(name) or _FMG.get(name) or _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
             raise TypeError(f"feanet_amd: no entry point fea_{name} that launches on a stream")
@@ -196,6 +204,11 @@ def exported_symbols():
     return names
 
 
+def fmg_exported_symbols():
+    """Every symbol declared in feanet_fmg.h."""
+    return [f"fea_{base}_{suf}" for base in _FMG for suf in ("f32", "f64")]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -215,7 +228,7 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = res
-    for base, sig in _SIGS.items():
+    for base, sig in list(_SIGS.items()) + list(_FMG.items()):
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")
             if fn is not None:

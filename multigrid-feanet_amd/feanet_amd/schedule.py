@@ -143,6 +143,13 @@ def vcycle_schedule(L, nu1=1, nu2=1, compat=None, start="a", tail_from=None, fus
     return steps, cur[0]
 
 
+def shift_schedule(steps, s):
+    """The steps of vcycle_schedule with every level index raised by s: the V-cycle of the sub-hierarchy s .. L-1
+    (L - s levels, level s its finest) in the solver's own level numbers, as the full-multigrid start runs it from
+    the stored iterate of level s (MultigridSolver.fmg).  tail_from of the sub-hierarchy is relative to s."""
+    return [(st[0], st[1] + s) + tuple(st[2:]) for st in steps]
+
+
 def hjac_schedule(L, nu1=1, nu2=1, start="a", tail_from=None, fuse=False):
     """V-cycle of M-FEANet-mg_test.ipynb MultiGrid.Step with mode='hjac' (:27346-27372 with Relax =
     HJacIterator.HRelax, :147-155): every relaxation is one learned-smoother sweep ("hsweep", l, src,

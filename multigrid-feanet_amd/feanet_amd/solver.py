@@ -27,7 +27,7 @@ import torch
 from . import _lib, mesh_setup as ms, ops
 from .graphs import GraphCache
 from .schedule import (OMDF, _other, extend_tail, group_hmid, group_mid, group_triples, hjac_schedule, pair_prolongations, pair_restrictions,
-                       vcycle_schedule)
+                       shift_schedule, vcycle_schedule)
 
 
 _SOLVERS = weakref.WeakValueDictionary()  # handle -> live MultigridSolver (torch.ops.feanet.mg_step)
@@ -891,6 +891,166 @@ class MultigridSolver:
                 self._run_graph(self._state, lambda: self._launch(plan))
             self._state = end
 
+    # ------------------------------------------------------------------ full multigrid (nested iteration)
+    FMG_MAX_COARSEST = 10  # interior nodes of the coarsest level fmg() accepts (4 x 7 nodes: the largest measured)
+
+    def fmg_base_cycles(self):
+        """Default number of cycles (nu1 + nu2 sweeps each) on the coarsest level of fmg(): 1 when that level has one
+        interior node (two sweeps solve it to 1/9), else 8."""
+        Lc = self.levels[-1]
+        return 1 if (Lc.H - 2) * (Lc.W - 2) == 1 else 8
+
+    def _fmg_check(self, cycles, interp, base_cycles):
+        if self.smoother != "jac":
+            raise ValueError("MultigridSolver.fmg: smoother='hjac' is not supported (Jacobi V-cycles only)")
+        if self.compat is not None:
+            raise ValueError(f"MultigridSolver.fmg: compat={self.compat!r} is not supported")
+        if self.zero_start:
+            raise ValueError("MultigridSolver.fmg: zero_start solvers have no stored iterate to start a cycle from")
+        if interp not in ("cubic", "bilinear"):
+            raise ValueError(f"MultigridSolver.fmg: interp must be 'cubic' or 'bilinear', not {interp!r}")
+        if int(cycles) < 1 or (base_cycles is not None and int(base_cycles) < 1):
+            raise ValueError("MultigridSolver.fmg: cycles and base_cycles must be >= 1")
+        Lc = self.levels[-1]
+        if (Lc.H - 2) * (Lc.W - 2) > self.FMG_MAX_COARSEST:
+            raise ValueError(f"MultigridSolver.fmg: the coarsest level ({Lc.H} x {Lc.W} nodes) is not solved by a few "
+                             f"sweeps; the hierarchy needs more levels (at most {self.FMG_MAX_COARSEST} interior nodes "
+                             "on the coarsest)")
+
+    def _fmg_tail(self, s):
+        """First level of the coarse tail in a V-cycle of the sub-hierarchy s .. L-1, or None: the solver's own tail,
+        or below it the levels s+1 .. L-1 where they fit in LDS."""
+        if self.tail_from is None or s + 1 > self.L - 1:
+            return None
+        t = max(self.tail_from, s + 1)
+        if t > self.tail_from:
+            Lv = self.levels[t]
+            need = _lib.coarse_tail_lds_bytes(Lv.H, Lv.W, self.L - t, Lv.esz, self.ntab > 1)
+            if not 0 < need <= _lib.TAIL_LDS_LIMIT:
+                return None
+        return t
+
+    def _fmg_subplan(self, s, start):
+        """One V-cycle of the sub-hierarchy s .. L-1 from level s's stored iterate in buffer `start`: (launches, end
+        buffer).  The schedule of L - s levels shifted by s, with each grouping of _build where its own predicate
+        holds (all of them bitwise the launches they replace).  Two kernels that sum a coarse value in different
+        orders (last-bit differences) are placed the same way in every solver, so that the pass gives the same bits
+        whichever performance switches the solver was built with: level s, the one with the stored iterate, always
+        runs its last pre-sweep fused with the residual + restriction (fea_mg_sweep_restrict), whatever `fuse`; the
+        levels below it, which pre-sweep more than once only with nu1 >= 2, always sweep and restrict in separate
+        launches — the arithmetic of the coarse tail, which is bitwise those and not the fused kernel.  For a fused
+        solver with nu1 <= 1 that is the ordinary plan at s = 0."""
+        if s == 0 and self.fuse and self.nu1 <= 1:
+            return self._plan(start)
+        key = ("fmg", s, start)
+        if key not in self._plans:
+            t = self._fmg_tail(s)
+            steps, end = vcycle_schedule(self.L - s, self.nu1, self.nu2, None, start, None if t is None else t - s,
+                                         True)
+            steps = shift_schedule(steps, s)
+            # nu1 >= 2: the levels below s sweep and restrict in separate launches, as the coarse tail computes them
+            steps = [x for st in steps for x in
+                     ([("sweep", st[1], st[2], st[3]), ("resid_restrict", st[1], st[3], None)]
+                      if st[0] == "sweep_restrict" and st[1] > s else [st])]
+            if self.mid:
+                steps = group_mid(steps, lambda lv: self._pick_mid(lv, False), lambda lv: self._pick_mid(lv, True))
+            if self.pair_levels:
+                if self.mid and t == self.tail_from:
+                    steps = group_triples(steps, lambda l: self.THREE_LEVEL_DOWN and self._three_level_ok(l),
+                                          lambda l: self.THREE_LEVEL_UP and self._three_level_ok(l))
+                ok = lambda l: l + 2 < self.L and self.levels[l + 2].H >= 3 and self.levels[l + 2].W >= 3
+                steps = pair_prolongations(pair_restrictions(steps, ok), ok)
+            if t == self.tail_from and self._tail_ext_ok():
+                steps = extend_tail(steps)
+            plan = [self.bind_step(st) for st in steps]
+            if t is not None and t > self.tail_from and self.tail_pid is not None:
+                # a tail that starts below tail_from: its levels' maps start further into tail_pid
+                off = sum(self.levels[j].H * self.levels[j].W for j in range(self.tail_from, t))
+                plan = [_lib.replace(rec, pid_levels=self.tail_pid.data_ptr() + off) if rec[0] == "mg_coarse_tail"
+                        else rec for rec in plan]
+            self._plans[key] = (plan, end)
+        return self._plans[key]
+
+    def _fmg_boundary(self, l, name, bc):
+        """fea_fmg_boundary on buffer `name` of level l: the Dirichlet data `bc` of the finest level sampled at this
+        level's nodes (bc None: zeros)."""
+        Lv = self.levels[l]
+        return _lib.launch("fmg_boundary", bc=None if bc is None else bc.data_ptr(),
+                           bc_bstride=0 if bc is None else self.H * self.W, stride=1 << l,
+                           dst=Lv.buf(name).data_ptr(), **Lv.geom_kw())
+
+    def fmg_program(self, cycles=1, interp="cubic", base_cycles=None):
+        """The launches of fmg() in order, as [(phase, level, launches)] with phase "restrict", "base" or "level",
+        and the finest-level buffer the result lands in.  (tools/fmg_timing.py times the phases.)"""
+        self._fmg_check(cycles, interp, base_cycles)
+        cycles = int(cycles)
+        base_cycles = self.fmg_base_cycles() if base_cycles is None else int(base_cycles)
+        lv, L, bc = self.levels, self.L, self._bc
+        order = 3 if interp == "cubic" else 1
+        prog = []
+        # the right-hand sides f_1 .. f_(L-1) = P^T f_(l-1)
+        chain = [_lib.launch("fmg_restrict", f=lv[l].f.data_ptr(), fc=lv[l + 1].f.data_ptr(), **lv[l].geom_kw(),
+                             **self._coarse_pitch(l)) for l in range(L - 1)]
+        if chain:
+            prog.append(("restrict", 0, chain))
+
+        def cycles_from(s, n):  # n V-cycles of the sub-hierarchy s .. L-1 from buffer a; the end buffer
+            out, cur = [], "a"
+            for _ in range(n):
+                plan, cur = self._fmg_subplan(s, cur)
+                out += plan
+            return out, cur
+
+        # coarsest level: its Dirichlet data, then base_cycles cycles from a zero interior (zeroed by the caller)
+        top = L - 1
+        launches = [self._fmg_boundary(top, "a", bc), self._fmg_boundary(top, "b", bc)]
+        if top == 0 and lv[0].c is not None:
+            launches.append(self._fmg_boundary(0, "c", bc))
+        body, cur = cycles_from(top, base_cycles)
+        prog.append(("base", top, launches + body))
+        for s in range(L - 2, -1, -1):
+            launches = [self._fmg_boundary(s, "a", bc), self._fmg_boundary(s, "b", bc)]
+            if s == 0 and lv[0].c is not None:
+                launches.append(self._fmg_boundary(0, "c", bc))
+            launches.append(_lib.launch("fmg_prolong", u=None, ec=lv[s + 1].buf(cur).data_ptr(),
+                                        out=lv[s].a.data_ptr(), **lv[s].geom_kw(), **self._coarse_pitch(s),
+                                        order=order))
+            # a level below the finest carries zero boundary values in every cycle that corrects with it
+            launches += [self._fmg_boundary(s + 1, "a", None), self._fmg_boundary(s + 1, "b", None)]
+            body, cur = cycles_from(s, cycles)
+            prog.append(("level", s, launches + body))
+        return prog, cur
+
+    def fmg(self, cycles=1, interp="cubic", base_cycles=None):
+        """Full-multigrid start (nested iteration; asynchronous, like vcycle): the problem of set_rhs / set_boundary
+        solved on the coarsest level (`base_cycles` cycles of nu1 + nu2 sweeps from zero; default
+        fmg_base_cycles()), then for every finer level the solution interpolated up as that level's guess
+        (interp "cubic" or "bilinear": fea_fmg_prolong) and `cycles` V-cycles of the levels from there down, with
+        the solver's own nu1, nu2, R, P and w.  Coarse right-hand sides are f_(l+1) = P^T f_l
+        (fea_fmg_restrict), coarse Dirichlet data the fine data injected at the coarse boundary nodes
+        (fea_fmg_boundary; taken off again before the level serves as a correction level).  Leaves the finest iterate
+        resident as load() does: vcycle, solve's loop, solution and residual_norm continue from it.  The result is
+        the same bits whichever of coarse_tail, mid, pair_levels and fuse the solver was built with.  The whole
+        program replays as one HIP graph per (cycles, interp, base_cycles).  About 4/3 of `cycles` fine V-cycles of
+        work; one pass with cubic interpolation ends below the discretisation error."""
+        prog, end = self.fmg_program(cycles, interp, base_cycles)
+        self._mid = None  # whatever iterate was in flight is replaced
+        launches = [rec for _, _, recs in prog for rec in recs]
+        coarsest = self.levels[-1]
+        base_cycles = self.fmg_base_cycles() if base_cycles is None else int(base_cycles)
+
+        def issue():
+            coarsest.a.zero_()  # the zero interior the base cycles start from (a few nodes; a memset node)
+            self._launch(launches)
+        # the launches hold the Dirichlet field's address: graphs of an earlier set_boundary are dropped
+        self._graphs.discard(lambda k: isinstance(k, tuple) and k[:1] == ("fmg",) and k[4] is not self._bc_version)
+        self._run_graph(("fmg", int(cycles), interp, base_cycles, self._bc_version, self.levels[0].c is not None),
+                        issue)
+        self._ab_bc, self._ab_version = self._bc, self._bc_version
+        if self.levels[0].c is not None:
+            self._c_bc = self._ab_version
+        self._state = end
+
     def step(self, u, f, cycles=1):
         """Functional form of MultiGrid.Step / MultiGrid.iterate: `cycles` V-cycles from u with rhs f,
         returns the new fine iterate — through the custom op torch.ops.feanet.mg_step (MultiGrid.iterate's
@@ -913,7 +1073,7 @@ class MultigridSolver:
             self.vcycle(cycles)
         return self.solution()
 
-    def solve(self, u0=None, f=None, F=None, eps=1e-6, max_cycles=100, bc_value=None):
+    def solve(self, u0=None, f=None, F=None, eps=1e-6, max_cycles=100, bc_value=None, fmg=False):
         """Driver loop of the reference notebooks (M-FEANet-mg_test.ipynb:27426-27436,
         MM_Model_convergence.ipynb:196-203): V-cycles until max_b ||r_b|| <= eps (at most max_cycles;
         stops after a non-finite norm, :27434-27436).  Returns (u [B,1,N,N], residual history: list of
@@ -922,13 +1082,21 @@ class MultigridSolver:
         Joinable solvers (V(1,1) Jacobi) run the device-resident loop of _solve_joined: the residual
         norm of every cycle comes out of the cycle join (fused, no extra pass) and the host looks at the
         history once per block of cycles.  The result — iterate and history — is that of the per-cycle
-        loop (bitwise the same iterate; norms summed in another fixed order)."""
+        loop (bitwise the same iterate; norms summed in another fixed order).
+
+        fmg=True (u0 must be None) starts from the full-multigrid pass fmg() instead of load(u0): history[0] is
+        the residual after that pass, and the per-cycle loop runs from there."""
+        if fmg and u0 is not None:
+            raise ValueError("MultigridSolver.solve: fmg=True computes its own start (u0 must be None)")
         if bc_value is not None:
             self.set_boundary(bc_value)
         if f is not None or F is not None:
             self.set_rhs(f=f, F=F)
-        self.load(u0)
-        if self._joinable() and not self._hjac_first and self.use_graph:
+        if fmg:
+            self.fmg()
+        else:
+            self.load(u0)
+        if not fmg and self._joinable() and not self._hjac_first and self.use_graph:
             return self._solve_joined(eps, max_cycles, u0)
         hist = [self.residual_norm().cpu().numpy()]
         while hist[-1].max() > eps and len(hist) <= max_cycles:
