@@ -137,8 +137,15 @@ _FMG = {
     "fmg_restrict": "P f, P fc, I B, I H, I W, I ld, LL bstride, I ldc, LL bstridec, P stream",
     "fmg_boundary": "P bc, LL bc_bstride, I stride, P dst, I B, I H, I W, I ld, LL bstride, P stream",
 }
+# the two-material set-up from an element phase image, declared in include/feanet_phase.h (dtype-free entry points,
+# full names as in _EXTRA, all returning int; tests/test_phase_host.py compares this table with that header)
+_PHASE = {
+    "fea_phase_pattern_map": "P phase, LL ldp, I He, I We, P pid, LL ldpid, P stream",
+    "fea_phase_coarsen": "P fine, LL ldf, I He, I We, P coarse, LL ldc, I min_count, P stream",
+}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
 _FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
+_PHASE = {name: sig.split(", ") for name, sig in _PHASE.items()}
 _SIGS = {name: sig.split(", ") for name, sig in _SIGS.items()}
 _EXTRA = {name: (sig.split(", ") if sig else [], res) for name, (sig, res) in _EXTRA.items()}
 
@@ -155,7 +162,7 @@ _NAMES = {}  # launch name -> parameter names in C-ABI order, without the traili
 def _names(name):
     """Parameter names of a launch record's entry point: a typed pair's base name, or a dtype-free fea_<name>."""
     if name not in _NAMES:
-        sig = _SIGS.get(name) or _FMG.get(name) or _EXTRA.get("fea_" + name, ([],))[0]
+        sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
             raise TypeError(f"feanet_amd: no entry point fea_{name} that launches on a stream")
@@ -209,6 +216,11 @@ def fmg_exported_symbols():
     return [f"fea_{base}_{suf}" for base in _FMG for suf in ("f32", "f64")]
 
 
+def phase_exported_symbols():
+    """Every symbol declared in feanet_phase.h."""
+    return list(_PHASE)
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -228,6 +240,11 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = res
+    for name, sig in _PHASE.items():
+        fn = sym(name)
+        if fn is not None:
+            fn.argtypes = _argtypes(sig)
+            fn.restype = I
     for base, sig in list(_SIGS.items()) + list(_FMG.items()):
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")

@@ -501,12 +501,16 @@ class DDSolver:
     overlaps the level-0 halo with the coarse levels instead; problem / prop / shape / size / R / P / w (the
     two-material problem on the square: each rank's levels carry their window of the global pattern maps) and
     smoother / hnet (the learned HRelax smoother, unjoined cycles) as MultigridSolver; other args as MultigridSolver.
+    An element phase image (MultigridSolver's phase=) is out of scope here: phase= raises ValueError.
     """
 
     def __init__(self, n, rows, rank, world, comm=None, agglomerate=None, dtype=torch.float64, device=None,
                  batch=1, nu1=1, nu2=1, fuse=True, graph=True, grid=None, overlap_l0=False, graph_min=5,
                  split_join=False, fold_gather=True, problem="poisson", prop=(1, 20), shape=0, size=2.0, R=None,
-                 P=None, w=(1.0, 1.0), smoother="jac", hnet=None):
+                 P=None, w=(1.0, 1.0), smoother="jac", hnet=None, phase=None):
+        if phase is not None:  # MultigridSolver(phase=...) / PCGSolver(phase=...): one GPU only
+            raise ValueError("DDSolver: phase (an element phase image) is not supported by the domain-decomposed "
+                             "solver; its two-material geometry is shape=0 / 1")
         self.n, self.m = n, rows
         self.overlap_l0 = overlap_l0
         self.graph_min = graph_min

@@ -87,6 +87,69 @@ def interface_pattern_map(N, shape=0, size=2.0):
     return pid
 
 
+def _phase_image(phase):
+    """A host phase image as a contiguous uint8 [m, n] array; ValueError unless 2-D with values in {0, 1}."""
+    a = np.asarray(phase)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"phase image must be [m, n] (one value per element), got shape {a.shape}")
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"phase image must be of bool or an integer dtype, got {a.dtype}")
+    if a.dtype != np.bool_ and a.size and (a.min() < 0 or a.max() > 1):
+        raise ValueError("phase image values must be 0 or 1 (two phases: 16 stencil rows hold the 2^4 patterns)")
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def phase_pattern_map(phase):
+    """uint8 [m+1, n+1] pattern id per node of an [m, n] element phase image (values 0 / 1), by
+    interface_pattern_map's rule applied to EVERY node: elements outside the domain count as phase 0, so a boundary
+    node gets the pattern of the elements it touches (the reference's pattern 0 there breaks K_ij == K_ji of the
+    one-row-per-node table once phase 1 reaches the boundary: stencil_mirror_mismatches).  On a centred inclusion
+    it equals interface_pattern_map bit for bit.  Two phases only."""
+    ph = np.pad(_phase_image(phase).astype(np.int64), 1)
+    code = ph[:-1, 1:] + 2 * ph[:-1, :-1] + 4 * ph[1:, :-1] + 8 * ph[1:, 1:]  # e1, e2, e3, e4 of node (r, c)
+    return _BITS_TO_ID[code]
+
+
+def coarsen_phase(phase, min_count):
+    """[m/2, n/2] uint8 image: a coarse element is phase 1 if at least `min_count` (1..4) of its 2 x 2 children are."""
+    ph = _phase_image(phase)
+    if ph.shape[0] % 2 or ph.shape[1] % 2:
+        raise ValueError(f"coarsen_phase: a {ph.shape[0]} x {ph.shape[1]} image has no 2 x 2 coarsening")
+    if int(min_count) not in (1, 2, 3, 4):
+        raise ValueError(f"coarsen_phase: min_count={min_count} is not in 1..4")
+    s = ph[0::2, 0::2].astype(np.int64) + ph[0::2, 1::2] + ph[1::2, 0::2] + ph[1::2, 1::2]
+    return (s >= int(min_count)).astype(np.uint8)
+
+
+PHASE_RULES = ("majority", "stiff")
+
+
+def phase_min_count(prop, rule):
+    """Phase-1 children a coarse element needs to be phase 1.  "stiff": a coarse element is stiff if any child is;
+    "majority": majority, ties to the stiffer phase.  Phase 1 is the stiffer one if prop[1] > prop[0]; with equal
+    coefficients either may be (the stencils are the same).  Rules that under-represent the stiff phase overshoot
+    the coarse correction (the stationary cycle diverges) and are not offered."""
+    if rule not in PHASE_RULES:
+        raise ValueError(f"unknown coarsen rule {rule!r} (one of {', '.join(map(repr, PHASE_RULES))})")
+    one_stiffer = float(prop[1]) > float(prop[0])
+    if rule == "stiff":
+        return 1 if one_stiffer else 4
+    return 2 if one_stiffer else 3
+
+
+def phase_hierarchy(phase, L, prop=(1, 20), rule="majority"):
+    """The L per-level phase images (uint8 numpy, finest first) of an [m, n] image, m and n divisible by 2^(L-1)."""
+    ph = _phase_image(phase)
+    s = 1 << (int(L) - 1)
+    if L < 1 or ph.shape[0] % s or ph.shape[1] % s:
+        raise ValueError(f"phase_hierarchy: {L} levels do not divide a {ph.shape[0]} x {ph.shape[1]} image")
+    k = phase_min_count(prop, rule)
+    out = [ph]
+    for _ in range(int(L) - 1):
+        out.append(coarsen_phase(out[-1], k))
+    return out
+
+
 def mass_stencil(h):
     """FNet consistent-mass stencil, float32 (FEANet/model.py:54-56)."""
     return np.array([[h * h / 36., h * h / 9., h * h / 36.],
@@ -124,6 +187,70 @@ def interface_pattern_map_device(N, shape=0, size=2.0, device="cuda", out=None, 
     rc = _lib.lib().fea_interface_pattern_map(base, int(ld), int(N), int(shape), float(size), st)
     if rc != 0:
         raise RuntimeError(f"feanet_amd: fea_interface_pattern_map failed ({rc})")
+    return out
+
+
+def _phase_tensor(phase, device=None):
+    """A device phase image as a contiguous uint8 [m, n] tensor (ValueError as _phase_image; the value check reads
+    one flag back).  A host image is checked on the host and copied once."""
+    import torch
+    if not torch.is_tensor(phase) or not phase.is_cuda:
+        a = _phase_image(phase.numpy() if torch.is_tensor(phase) else phase)
+        return torch.from_numpy(a).to(device if device is not None else "cuda")
+    if phase.dim() != 2 or phase.shape[0] < 1 or phase.shape[1] < 1:
+        raise ValueError(f"phase image must be [m, n] (one value per element), got shape {tuple(phase.shape)}")
+    if phase.dtype.is_floating_point or phase.dtype.is_complex:
+        raise ValueError(f"phase image must be of bool or an integer dtype, got {phase.dtype}")
+    if phase.dtype != torch.bool and bool(((phase < 0) | (phase > 1)).any().item()):
+        raise ValueError("phase image values must be 0 or 1 (two phases: 16 stencil rows hold the 2^4 patterns)")
+    if device is not None and phase.device != torch.device(device):
+        phase = phase.to(device)
+    return phase.to(torch.uint8).contiguous()
+
+
+def phase_pattern_map_device(phase, out=None, ld=None):
+    """phase_pattern_map on the GPU (phase_ops.hip, fea_phase_pattern_map): `phase` a contiguous uint8 [m, n] device
+    tensor.  Returns a uint8 [m+1, n+1] tensor, or writes rows of pitch `ld` bytes starting at address / tensor `out`
+    (e.g. base + ld + off of a framed pattern map: its ghost ring and pad columns are not touched) and returns it."""
+    import torch
+    from . import _lib
+    m, n = phase.shape
+    if phase.dtype != torch.uint8 or not phase.is_contiguous():
+        raise ValueError("phase_pattern_map_device: a contiguous uint8 device image (see _phase_tensor)")
+    if out is None:
+        out = torch.empty((m + 1, n + 1), dtype=torch.uint8, device=phase.device)
+        ld = n + 1
+    base = out.data_ptr() if isinstance(out, torch.Tensor) else int(out)
+    st = torch.cuda.current_stream(phase.device).cuda_stream
+    rc = _lib.lib().fea_phase_pattern_map(phase.data_ptr(), n, m, n, base, int(ld), st)
+    if rc != 0:
+        raise RuntimeError(f"feanet_amd: fea_phase_pattern_map failed ({rc})")
+    return out
+
+
+def coarsen_phase_device(phase, min_count):
+    """coarsen_phase on the GPU (fea_phase_coarsen): uint8 [m, n] device tensor -> uint8 [m/2, n/2] device tensor."""
+    import torch
+    from . import _lib
+    m, n = phase.shape
+    if phase.dtype != torch.uint8 or not phase.is_contiguous():
+        raise ValueError("coarsen_phase_device: a contiguous uint8 device image (see _phase_tensor)")
+    if m % 2 or n % 2:
+        raise ValueError(f"coarsen_phase: a {m} x {n} image has no 2 x 2 coarsening")
+    out = torch.empty((m // 2, n // 2), dtype=torch.uint8, device=phase.device)
+    st = torch.cuda.current_stream(phase.device).cuda_stream
+    rc = _lib.lib().fea_phase_coarsen(phase.data_ptr(), n, m, n, out.data_ptr(), n // 2, int(min_count), st)
+    if rc != 0:
+        raise RuntimeError(f"feanet_amd: fea_phase_coarsen failed ({rc})")
+    return out
+
+
+def phase_hierarchy_device(phase, L, prop=(1, 20), rule="majority"):
+    """phase_hierarchy on the GPU: list of L uint8 device tensors, `phase` (from _phase_tensor) first."""
+    k = phase_min_count(prop, rule)
+    out = [phase]
+    for _ in range(int(L) - 1):
+        out.append(coarsen_phase_device(out[-1], k))
     return out
 
 

@@ -43,7 +43,9 @@ _KRYLOV = ("pcg_residual", "pcg_dot", "pcg_direction", "pcg_update")  # launched
 class PCGSolver:
     """Multigrid-preconditioned conjugate gradients for MultigridSolver's problems (one GPU).
 
-    Args as MultigridSolver (n, levels, problem, dtype, batch, omega, size, prop, shape, rows, R, P, w), and
+    Args as MultigridSolver (n, levels, problem, dtype, batch, omega, size, prop, shape, rows, R, P, w, and the
+    element phase image phase / coarsen / phase_levels of the two-material problem, with its limits: two phases, one
+    image for the whole batch), and
         nu: pre- and post-sweeps of the preconditioning V(nu, nu) cycle (equal, so the cycle is symmetric).
         graph: replay blocks of iterations as HIP graphs.
         check_every: solve() reads the samples' done flags every this many iterations, and at no other time.
@@ -62,7 +64,8 @@ class PCGSolver:
 
     def __init__(self, n, levels=None, problem="poisson", dtype=torch.float64, device=None, batch=1,
                  omega=2.0 / 3.0, size=2.0, prop=(1, 20), shape=0, rows=None, R=None, P=None, w=(1.0, 1.0), nu=1,
-                 graph=True, check_every=8, smoother="jac", compat=None, precond_dtype=None):
+                 graph=True, check_every=8, smoother="jac", compat=None, precond_dtype=None, phase=None,
+                 coarsen="majority", phase_levels=None):
         pdt = dtype if precond_dtype is None else precond_dtype
         for name, d in (("dtype", dtype), ("precond_dtype", pdt)):
             if d not in (torch.float32, torch.float64):
@@ -90,7 +93,8 @@ class PCGSolver:
             raise ValueError("PCGSolver: the ratios w must be positive")
         self.mg = MultigridSolver(n, levels=levels, problem=problem, dtype=pdt, device=device, batch=batch,
                                   omega=omega, size=size, prop=prop, shape=shape, R=R, P=P, w=w, nu1=int(nu),
-                                  nu2=int(nu), graph=False, rows=rows, zero_start=True, smoother="jac")
+                                  nu2=int(nu), graph=False, rows=rows, zero_start=True, smoother="jac", phase=phase,
+                                  coarsen=coarsen, phase_levels=phase_levels)
         mg = self.mg
         self.device, self.dtype, self.B = mg.device, dtype, mg.B
         self.mixed = pdt != dtype
@@ -101,8 +105,11 @@ class PCGSolver:
         if self.mixed:
             # the Krylov fields' own fp64 frame: its three fields are r, x and b, and its pattern map and stencil
             # table are kapply<double>'s (pattern windows hold byte offsets of sizeof(T) table rows)
-            self.L0 = L0 = _Level(mg.m, mg.n, self.B, dtype, self.device,
-                                  pid_shape=(shape, size) if problem == "interface" else None)
+            if mg.phase_images is not None:  # the same fine image, on the device
+                self.L0 = L0 = _Level(mg.m, mg.n, self.B, dtype, self.device, pid_phase=mg.phase_images[0])
+            else:
+                self.L0 = L0 = _Level(mg.m, mg.n, self.B, dtype, self.device,
+                                      pid_shape=(shape, size) if problem == "interface" else None)
             self.ktab = torch.from_numpy(mg.ktab_np.reshape(-1, 9).astype(np.float64)).to(self.device)
             self.r, self.x, self.b = L0.f, L0.a, L0.b
             p0, p1 = (torch.zeros_like(L0.a) for _ in range(2))

@@ -58,7 +58,7 @@ def solver_by_handle(h):
 class _Level:
     """Framed buffers of one level: H x W nodes (H = rows, W = columns)."""
 
-    def __init__(self, m, n, B, dtype, device, pid_np=None, pid_shape=None):
+    def __init__(self, m, n, B, dtype, device, pid_np=None, pid_shape=None, pid_phase=None):
         self.m, self.n = m, n
         self.H, self.W = m + 1, n + 1
         self.N = self.W
@@ -84,6 +84,9 @@ class _Level:
             self.pid = torch.zeros((self.H + 2) * self.ld + 256, dtype=torch.uint8, device=device)
             ms.interface_pattern_map_device(self.N, pid_shape[0], pid_shape[1], device=device,
                                             out=self.pid.data_ptr() + self.ld + self.off, ld=self.ld)
+        elif pid_phase is not None:  # this level's [m, n] uint8 device phase image: likewise, boundary nodes included
+            self.pid = torch.zeros((self.H + 2) * self.ld + 256, dtype=torch.uint8, device=device)
+            ms.phase_pattern_map_device(pid_phase, out=self.pid.data_ptr() + self.ld + self.off, ld=self.ld)
 
     def buf(self, name):
         if name in ("zero", "c") and getattr(self, name) is None:
@@ -151,6 +154,21 @@ class MultigridSolver:
         pid_maps: two-material problem only — explicit per-level pattern maps ([H_l, W_l] uint8, one per level)
             instead of the MeshCenterInterface maps of the square: a domain-decomposed rank's window of the
             global level maps (feanet_amd.dd.DDSolver(problem="interface")); allows a rectangular window.
+        phase: two-material problem only — the geometry as an element phase image instead of `shape`: [rows, n], one
+            value per element, 0 (coefficient prop[0]) or 1 (prop[1]); numpy array or tensor, host or device, bool or
+            any integer dtype.  A device image stays on the device: pattern maps and coarse images are built there
+            (fea_phase_pattern_map / fea_phase_coarsen).  Every node, boundary nodes included, takes the pattern of
+            the elements it touches (mesh_setup.phase_pattern_map), so phase 1 may touch the boundary.  Rectangles
+            and sizes that are not powers of two as `rows` / `n` allow; rows and n divisible by 2^(L-1).
+        coarsen: how level l+1's image follows from level l's, as a count of phase-1 children per coarse element
+            (mesh_setup.phase_min_count).  "majority": ties to the stiffer phase — the reference's rates on smooth
+            inclusions, but the stationary cycle can diverge on element-scale noise.  "stiff": stiff if any child
+            is — never diverged at contrast 20 in the study of DESIGN, slower on smooth inclusions.  Neither is
+            mesh-independent at high contrast (prop=(1, 1000)): solve there with PCGSolver.
+        phase_levels: explicit list of L per-level images instead of coarsening (phase_levels[0] must equal `phase`
+            if both are given).
+        Not supported with a phase image: more than two phases (16 table rows hold exactly 2^4 patterns), one image
+        per sample of a batch (the kernels broadcast one map), DDSolver, and the FEANet/ drop-in classes.
     """
 
     MID_NODES = 20000     # levels with <= this many nodes (B*H*W) may go to the LDS-tile multi-level launches (groups
@@ -184,7 +202,8 @@ class MultigridSolver:
     def __init__(self, n, levels=None, problem="poisson", dtype=torch.float64, device=None, batch=1,
                  omega=2.0 / 3.0, size=2.0, prop=(1, 20), shape=0, R=None, P=None, w=(1.0, 1.0),
                  nu1=1, nu2=1, compat=None, graph=True, coarse_tail=True, fuse=True, rows=None, zero_start=False,
-                 smoother="jac", hnet=None, join_cycles=True, mid=True, pair_levels=True, pid_maps=None):
+                 smoother="jac", hnet=None, join_cycles=True, mid=True, pair_levels=True, pid_maps=None,
+                 phase=None, coarsen="majority", phase_levels=None):
         m = n if rows is None else int(rows)
         if rows is None and (n < 2 or (n & (n - 1)) != 0):
             raise ValueError(f"MultigridSolver: n={n} must be a power of two >= 2")
@@ -192,6 +211,33 @@ class MultigridSolver:
             raise ValueError(f"MultigridSolver: need >= 2 intervals each way (got {m} x {n})")
         if dtype not in (torch.float32, torch.float64):
             raise TypeError("MultigridSolver: dtype must be torch.float32 or torch.float64")
+        if coarsen not in ms.PHASE_RULES:
+            raise ValueError(f"MultigridSolver: unknown coarsen rule {coarsen!r}")
+        imaged = phase is not None or phase_levels is not None
+        if imaged:  # refused before the device is touched; values of a device image after
+            if problem != "interface":
+                raise ValueError("MultigridSolver: phase / phase_levels are for problem='interface'")
+            if pid_maps is not None:
+                raise ValueError("MultigridSolver: give phase or pid_maps, not both")
+            if shape != 0:
+                raise ValueError("MultigridSolver: give phase or shape, not both (a phase image is the geometry)")
+            as_array = lambda p: p if torch.is_tensor(p) else np.asarray(p)
+            phase = None if phase is None else as_array(phase)
+            phase_levels = None if phase_levels is None else [as_array(p) for p in phase_levels]
+            if phase_levels is not None and not phase_levels:
+                raise ValueError("MultigridSolver: phase_levels is empty")
+            for name, img in [("phase", phase)] + [(f"phase_levels[{l}]", p) for l, p in enumerate(phase_levels or [])]:
+                if img is None:
+                    continue
+                if len(img.shape) != 2:
+                    raise ValueError(f"MultigridSolver: {name} must be [rows, n] (one value per element), got shape "
+                                     f"{tuple(img.shape)}")
+                if not (torch.is_tensor(img) and img.is_cuda):
+                    ms._phase_image(img.numpy() if torch.is_tensor(img) else img)
+            fine = phase if phase is not None else phase_levels[0]
+            if tuple(fine.shape) != (m, n):
+                raise ValueError(f"MultigridSolver: the phase image is {tuple(fine.shape)}, the grid has {m} x {n} "
+                                 "elements (rows x n)")
         self.device = torch.device(device if device is not None else "cuda")
         ops.require_hip(torch.empty(0, device=self.device), "solver device")
         self.n, self.m = n, m
@@ -236,7 +282,7 @@ class MultigridSolver:
         multi = problem == "interface"
         if problem not in ("poisson", "interface"):
             raise ValueError(f"MultigridSolver: unknown problem {problem!r}")
-        if multi and m != n and pid_maps is None:
+        if multi and m != n and pid_maps is None and not imaged:
             raise ValueError("MultigridSolver: the two-material problem is defined on the square only")
         if pid_maps is not None:  # explicit per-level maps (a domain-decomposed rank's window of the global maps)
             if not multi:
@@ -268,8 +314,12 @@ class MultigridSolver:
         self.rtab = torch.from_numpy(np.ascontiguousarray(R).reshape(-1, 9).astype(npdt)).to(dev)
         self.ptab = torch.from_numpy(np.ascontiguousarray(P).reshape(-1, 9).astype(npdt)).to(dev)
         self.levels = []
+        self.phase_images = self._phase_images(phase, phase_levels, prop, coarsen) if imaged else None
         for l in range(self.L):
             nl, ml = n >> l, m >> l
+            if imaged:  # pattern maps straight from the level's image into the frame, on the device
+                self.levels.append(_Level(ml, nl, self.B, dtype, dev, pid_phase=self.phase_images[l]))
+                continue
             if pid_maps is not None:
                 if pid_maps[l].shape != (ml + 1, nl + 1):
                     raise ValueError(f"MultigridSolver: pid_maps[{l}] is {pid_maps[l].shape}, level {l} is "
@@ -278,7 +328,9 @@ class MultigridSolver:
                 continue
             # two-material pattern maps: built on the device (setup_ops.hip), bit-identical to the host
             self.levels.append(_Level(ml, nl, self.B, dtype, dev, pid_shape=(shape, size) if multi else None))
-        if pid_maps is not None:
+        if imaged:
+            self.fine_pid = self.levels[0].pid_view().contiguous()
+        elif pid_maps is not None:
             self.fine_pid = torch.from_numpy(pid_maps[0]).to(dev)
         else:
             self.fine_pid = ms.interface_pattern_map_device(n + 1, shape, size, device=dev) if multi else None
@@ -306,7 +358,9 @@ class MultigridSolver:
                     self.hjac_tail_from = l
                     break
         t_from = self.tail_from if self.tail_from is not None else self.hjac_tail_from
-        if t_from is not None and multi:
+        if t_from is not None and imaged:
+            self.tail_pid = torch.cat([self.levels[l].pid_view().reshape(-1) for l in range(t_from, self.L)])
+        elif t_from is not None and multi:
             maps = [pid_maps[l].reshape(-1) if pid_maps is not None else
                     ms.interface_pattern_map(self.levels[l].N, shape, size).reshape(-1) for l in range(t_from, self.L)]
             self.tail_pid = torch.from_numpy(np.concatenate(maps)).to(dev)
@@ -340,6 +394,25 @@ class MultigridSolver:
         self.mass = ms.mass_stencil(size / n)
         self.handle = next(_HANDLES)  # torch.ops.feanet.mg_step(u, f, handle, cycles)
         _SOLVERS[self.handle] = self
+
+    def _phase_images(self, phase, phase_levels, prop, coarsen):
+        """The L per-level phase images as contiguous uint8 device tensors: `phase_levels`, or `phase` coarsened on
+        the device by the rule's child count.  Host images are copied once; a device image never leaves it.  (The
+        constructor has checked that rows and n are divisible by 2^(L-1) and that the finest image is [rows, n].)"""
+        m, n, L, dev = self.m, self.n, self.L, self.device
+        fine = None if phase is None else ms._phase_tensor(phase, dev)
+        if phase_levels is None:
+            return ms.phase_hierarchy_device(fine, L, prop, coarsen)
+        if len(phase_levels) != L:
+            raise ValueError(f"MultigridSolver: {len(phase_levels)} phase_levels for {L} levels")
+        imgs = [ms._phase_tensor(p, dev) for p in phase_levels]
+        for l, p in enumerate(imgs):
+            if tuple(p.shape) != (m >> l, n >> l):
+                raise ValueError(f"MultigridSolver: phase_levels[{l}] is {tuple(p.shape)}, level {l} has "
+                                 f"{(m >> l, n >> l)} elements")
+        if fine is not None and not torch.equal(fine, imgs[0]):
+            raise ValueError("MultigridSolver: phase_levels[0] differs from phase")
+        return imgs
 
     # ------------------------------------------------------------------ problem data
     @property
