@@ -3,6 +3,8 @@
   feanet_amd.ops          tensor-level HIP operators (KNet apply, Jacobi sweep, R, P, norms)
   feanet_amd.solver       MultigridSolver: fused-kernel V-cycle over framed level buffers
   feanet_amd.pcg          PCGSolver: conjugate gradients preconditioned by that V-cycle
+  feanet_amd.flux         element fluxes q = -k grad u, mean flux / gradient, energy of a field (element_flux)
+  feanet_amd.homogenize   effective_conductivity of a phase image from two load cases
   feanet_amd.graphs       GraphCache: eager once, captured as a HIP graph the second time, replayed after
   feanet_amd.mesh_setup  vectorised discretisation tables (pattern maps, stencils)
   FEANet.*                drop-in modules with the reference's names (sibling package)
@@ -18,7 +20,13 @@ def __getattr__(name):
     if name == "PCGSolver":
         from .pcg import PCGSolver
         return PCGSolver
-    if name in ("ops", "solver", "pcg", "_lib"):
+    if name == "element_flux":
+        from .flux import element_flux
+        return element_flux
+    if name == "effective_conductivity":
+        from .homogenize import effective_conductivity
+        return effective_conductivity
+    if name in ("ops", "solver", "pcg", "_lib", "flux", "homogenize"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

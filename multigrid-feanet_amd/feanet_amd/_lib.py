@@ -143,7 +143,18 @@ _PHASE = {
     "fea_phase_pattern_map": "P phase, LL ldp, I He, I We, P pid, LL ldpid, P stream",
     "fea_phase_coarsen": "P fine, LL ldf, I He, I We, P coarse, LL ldc, I min_count, P stream",
 }
+# the element flux fields and sums, declared in include/feanet_flux.h (tests/test_flux_host.py compares this table
+# with that header): "flux" a typed pair in the field syntax of _SIGS, the fea_* names dtype-free entry points as in
+# _EXTRA, with their return types in _FLUX_RES
+_FLUX = {
+    "flux": "P u, P phase, LL ldp, D k0, D k1, D h, P q, LL ldq, LL cstride, LL qbstride, P part, I B, I H, I W, "
+            "I ld, LL bstride, P stream",
+    "fea_flux_parts": "I H, I W, I elem_size",
+    "fea_flux_final": "P part, LL per, P sums, I B, P stream",
+}
+_FLUX_RES = {"fea_flux_parts": LL, "fea_flux_final": I}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
+_FLUX = {name: sig.split(", ") for name, sig in _FLUX.items()}
 _FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
 _PHASE = {name: sig.split(", ") for name, sig in _PHASE.items()}
 _SIGS = {name: sig.split(", ") for name, sig in _SIGS.items()}
@@ -162,7 +173,8 @@ _NAMES = {}  # launch name -> parameter names in C-ABI order, without the traili
 def _names(name):
     """Parameter names of a launch record's entry point: a typed pair's base name, or a dtype-free fea_<name>."""
     if name not in _NAMES:
-        sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _EXTRA.get("fea_" + name, ([],))[0]
+        sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _FLUX.get(name) or \
+            _FLUX.get("fea_" + name) or _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
             raise TypeError(f"feanet_amd: no entry point fea_{name} that launches on a stream")
@@ -221,6 +233,14 @@ def phase_exported_symbols():
     return list(_PHASE)
 
 
+def flux_exported_symbols():
+    """Every symbol declared in feanet_flux.h."""
+    names = []
+    for n in _FLUX:
+        names += [n] if n.startswith("fea_") else [f"fea_{n}_f32", f"fea_{n}_f64"]
+    return names
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -245,7 +265,13 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = I
-    for base, sig in list(_SIGS.items()) + list(_FMG.items()):
+    for name, res in _FLUX_RES.items():
+        fn = sym(name)
+        if fn is not None:
+            fn.argtypes = _argtypes(_FLUX[name])
+            fn.restype = res
+    typed_flux = [(n, sig) for n, sig in _FLUX.items() if n not in _FLUX_RES]
+    for base, sig in list(_SIGS.items()) + list(_FMG.items()) + typed_flux:
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")
             if fn is not None:

@@ -284,6 +284,14 @@ class PCGSolver:
         _lib.call("mg_unpack", self.dtype, self.x.data_ptr(), out.data_ptr(), *L0.geom(), self._stream())
         return out
 
+    def flux(self, fields=True):
+        """Element fluxes, their means, the mean gradient and the energy of the current iterate x (mixed precision:
+        the fp64 x), as MultigridSolver.flux; no host synchronisation."""
+        from . import flux as fx
+        img, k0, k1 = self.mg.flux_image()
+        return fx.flux_framed(self.x.data_ptr(), self.dtype, self.device, *self.L0.geom(), phase=img, k0=k0, k1=k1,
+                              h=self.mg.size / self.mg.n, fields=fields)
+
     def residual_norm(self):
         """Per-sample true residual ||(b - K x)[1:-1, 1:-1]||_2 (float64 device tensor [B]), recomputed from x."""
         mg, L0 = self.mg, self.L0

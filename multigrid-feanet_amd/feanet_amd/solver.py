@@ -256,6 +256,9 @@ class MultigridSolver:
         self.omega = omega
         self.size = size
         self.problem = problem
+        self.prop, self.shape = (prop[0], prop[1]), shape
+        self._flux_image = None  # flux(): the fine element phase image on the device (built on first use)
+        self._explicit_maps = pid_maps is not None
         self.nu1, self.nu2 = int(nu1), int(nu2)
         self.compat = compat
         self.use_graph = graph
@@ -505,6 +508,31 @@ class MultigridSolver:
         _lib.call("mg_unpack", self.dtype, L0.buf(self._iterate()).data_ptr(), out.data_ptr(), *L0.geom(),
                   ops._stream(out))
         return out
+
+    def flux_image(self):
+        """(phase image, k0, k1) of flux(): the device-resident fine image of a phase= solver, element_phase(N, shape,
+        size) copied once for a shape= solver, no image and k = 1 for the Poisson problem."""
+        from . import flux as fx
+        if self.problem != "interface":
+            return None, 1.0, 1.0
+        if self._flux_image is None:
+            if self.phase_images is not None:
+                self._flux_image = self.phase_images[0]
+            elif self._explicit_maps or self.m != self.n:
+                raise ValueError("MultigridSolver.flux: a solver built from pid_maps has no element phase image")
+            else:
+                self._flux_image = fx.phase_operand(ms.element_phase(self.N, self.shape, self.size), self.m, self.n,
+                                                    self.device)
+        return (self._flux_image,) + fx.coefficients(self.prop)
+
+    def flux(self, fields=True):
+        """Element fluxes q = -k grad u, their means, the mean gradient and the energy u^T K u of the current iterate
+        (the buffer solution() reads), as a feanet_amd.flux.FluxResult of device tensors; no host synchronisation."""
+        from . import flux as fx
+        L0 = self.levels[0]
+        img, k0, k1 = self.flux_image()
+        return fx.flux_framed(L0.buf(self._iterate()).data_ptr(), self.dtype, self.device, *L0.geom(), phase=img,
+                              k0=k0, k1=k1, h=self.size / self.n, fields=fields)
 
     def residual_norm(self):
         """Per-sample ||(f - K u)[1:-1, 1:-1]||_2 of the current iterate (float64 device tensor [B])."""
