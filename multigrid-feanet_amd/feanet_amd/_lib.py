@@ -153,7 +153,17 @@ _FLUX = {
     "fea_flux_final": "P part, LL per, P sums, I B, P stream",
 }
 _FLUX_RES = {"fea_flux_parts": LL, "fea_flux_final": I}
+# the bilinear energy forms and their element densities, declared in include/feanet_energy.h (tests/
+# test_energy_host.py compares this table with that header), in the form of _FLUX / _FLUX_RES
+_ENERGY = {
+    "energy": "P u, P v, P phase, LL ldp, P dens, LL ldd, LL cstride, LL dbstride, P part, I B, I H, I W, I ld, "
+              "LL ubstride, LL vbstride, P stream",
+    "fea_energy_parts": "I H, I W, I elem_size",
+    "fea_energy_final": "P part, LL per, P sums, I B, P stream",
+}
+_ENERGY_RES = {"fea_energy_parts": LL, "fea_energy_final": I}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
+_ENERGY = {name: sig.split(", ") for name, sig in _ENERGY.items()}
 _FLUX = {name: sig.split(", ") for name, sig in _FLUX.items()}
 _FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
 _PHASE = {name: sig.split(", ") for name, sig in _PHASE.items()}
@@ -174,7 +184,8 @@ def _names(name):
     """Parameter names of a launch record's entry point: a typed pair's base name, or a dtype-free fea_<name>."""
     if name not in _NAMES:
         sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _FLUX.get(name) or \
-            _FLUX.get("fea_" + name) or _EXTRA.get("fea_" + name, ([],))[0]
+            _FLUX.get("fea_" + name) or _ENERGY.get(name) or _ENERGY.get("fea_" + name) or \
+            _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
             raise TypeError(f"feanet_amd: no entry point fea_{name} that launches on a stream")
@@ -241,6 +252,14 @@ def flux_exported_symbols():
     return names
 
 
+def energy_exported_symbols():
+    """Every symbol declared in feanet_energy.h."""
+    names = []
+    for n in _ENERGY:
+        names += [n] if n.startswith("fea_") else [f"fea_{n}_f32", f"fea_{n}_f64"]
+    return names
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -265,12 +284,14 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = I
-    for name, res in _FLUX_RES.items():
-        fn = sym(name)
-        if fn is not None:
-            fn.argtypes = _argtypes(_FLUX[name])
-            fn.restype = res
+    for table, results in ((_FLUX, _FLUX_RES), (_ENERGY, _ENERGY_RES)):
+        for name, res in results.items():
+            fn = sym(name)
+            if fn is not None:
+                fn.argtypes = _argtypes(table[name])
+                fn.restype = res
     typed_flux = [(n, sig) for n, sig in _FLUX.items() if n not in _FLUX_RES]
+    typed_flux += [(n, sig) for n, sig in _ENERGY.items() if n not in _ENERGY_RES]
     for base, sig in list(_SIGS.items()) + list(_FMG.items()) + typed_flux:
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")

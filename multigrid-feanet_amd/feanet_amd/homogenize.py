@@ -5,6 +5,11 @@ Two load cases on one image, as one batch of two samples: f = 0 and the linear f
 flux, K_eff[:, j] = -<q>_j.  The linear field is also the initial guess, so a homogeneous image starts with r0 = 0
 and the conjugate gradient freezes it in its INIT step.
 
+route="energy"  evaluates the same two solved fields through the energy form instead:
+K_E[i, j] = a(u_i, u_j) / |V| with a(u, v) = sum_e k_e u_e^T Ke v_e.  It is symmetric by construction, its error is
+quadratic in the error of the iterate (one-sided on the diagonal), and its derivative with respect to the coefficient
+of a phase, or of one element, needs no further solve.
+
 Grid axes: index 0 is the row direction, index 1 the column direction.
 """
 from collections import namedtuple
@@ -20,6 +25,16 @@ identity).  iterations, flags: per load case (flags: 1 converged, 2 breakdown, 0
 flags are 1."""
 
 
+EnergyHomogenizationResult = namedtuple(
+    "EnergyHomogenizationResult", "K_eff dK_dprop sensitivity K_eff_flux route_gap iterations flags converged")
+EnergyHomogenizationResult.__doc__ = """K_eff: [2, 2] float64 host array, (k0 A_0 + k1 A_1) / |V| with k0, k1 the
+float32-rounded prop and |V| = m n h^2; exactly symmetric.  dK_dprop: [2 phases, 2, 2], A_p / |V|, the derivative of
+K_eff with respect to prop[p].  sensitivity: device tensor [3, m, n] in the solver's dtype, the derivative of
+K_eff[0, 0], K_eff[0, 1], K_eff[1, 1] with respect to each element's own coefficient (the element density / |V|), or
+None (fields=False).  K_eff_flux: the flux route's tensor from the same solve; route_gap: max|K_eff -
+sym(K_eff_flux)| / max|K_eff|.  iterations, flags, converged: as in HomogenizationResult."""
+
+
 def load_cases(m, n, size, dtype, device):
     """[2, 1, m+1, n+1]: u = r h and u = c h, h = size / n."""
     h = size / n
@@ -30,16 +45,20 @@ def load_cases(m, n, size, dtype, device):
 
 
 def effective_conductivity(phase, prop=(1, 20), size=2.0, dtype=torch.float64, method="pcg", rtol=1e-10,
-                           max_iters=200, coarsen="stiff", device=None, **solver_kw):
+                           max_iters=200, coarsen="stiff", device=None, route="flux", fields=True, **solver_kw):
     """K_eff of the [m, n] element phase image `phase` (host or device; 0 -> prop[0], 1 -> prop[1]) on the rectangle of
     width `size` (h = size / n).  method "pcg": PCGSolver (solver_kw e.g. precond_dtype=torch.float32); "mg":
     MultigridSolver's stationary cycles (all samples run until the slowest is done; a sample whose ||r0|| is at the
     rounding level of the residual counts as solved).  Every sample stops at ||r|| <= rtol ||r0||.  Raises
-    RuntimeError if a sample broke down; samples that did not converge in max_iters are reported in flags / converged, not hidden."""
+    RuntimeError if a sample broke down; samples that did not converge in max_iters are reported in flags / converged, not hidden.
+    route "flux": K_eff[:, j] = -<q>_j, a HomogenizationResult.  route "energy": K_eff from the energy form of the same
+    two fields with its derivatives, an EnergyHomogenizationResult (fields=False: without the element sensitivity)."""
     from .pcg import PCGSolver
     from .solver import MultigridSolver
     if method not in ("pcg", "mg"):
         raise ValueError(f"effective_conductivity: unknown method {method!r} ('pcg' or 'mg')")
+    if route not in ("flux", "energy"):
+        raise ValueError(f"effective_conductivity: unknown route {route!r} ('flux' or 'energy')")
     if len(phase.shape) != 2:
         raise ValueError(f"effective_conductivity: phase must be [rows, n], got shape {tuple(phase.shape)}")
     m, n = (int(v) for v in phase.shape)
@@ -77,6 +96,18 @@ def effective_conductivity(phase, prop=(1, 20), size=2.0, dtype=torch.float64, m
         raise RuntimeError(f"effective_conductivity: the solve broke down (flags {flags.tolist()}); contrast "
                            f"{prop}, method {method!r}")
     res = s.flux(fields=False)
+    if route == "energy":
+        from .flux import coefficients
+        forms = s.energy_forms(pair=(0, 1), fields=fields)
+        vol = m * n * h * h
+        A = forms.A[0].cpu().numpy()
+        dK = np.stack([np.array([[a[0], a[1]], [a[1], a[2]]]) for a in A]) / vol
+        k0, k1 = coefficients(prop)
+        K_E = k0 * dK[0] + k1 * dK[1]
+        K_flux = -res.mean_flux.cpu().numpy().T.copy()
+        gap = float(np.abs(K_E - 0.5 * (K_flux + K_flux.T)).max() / np.abs(K_E).max())
+        sens = None if forms.density is None else forms.density[0] / vol
+        return EnergyHomogenizationResult(K_E, dK, sens, K_flux, gap, iters, flags, bool((flags == 1).all()))
     mean_flux = res.mean_flux.cpu().numpy()
     mean_grad = res.mean_grad.cpu().numpy()
     energy = res.energy.cpu().numpy()
@@ -84,3 +115,33 @@ def effective_conductivity(phase, prop=(1, 20), size=2.0, dtype=torch.float64, m
     hill = np.abs(energy + m * n * h * h * (G * mean_flux).sum(1)) / energy
     return HomogenizationResult(-mean_flux.T.copy(), mean_flux, mean_grad, energy, hill, iters, flags,
                                 bool((flags == 1).all()))
+
+
+class _EffectiveConductivity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prop, phase, kw):
+        res = effective_conductivity(phase, prop=tuple(float(p) for p in prop.detach().cpu()), route="energy",
+                                     fields=False, **kw)
+        if not res.converged:
+            raise RuntimeError(f"effective_conductivity_torch: the solve did not converge (flags {res.flags.tolist()})")
+        ctx.dK = torch.from_numpy(res.dK_dprop)
+        return torch.from_numpy(res.K_eff).to(prop.device)
+
+    @staticmethod
+    def backward(ctx, grad):
+        dK = ctx.dK.to(grad.device)
+        return (dK * grad.to(dK.dtype)).sum((1, 2)), None, None
+
+
+def effective_conductivity_torch(phase, prop_tensor, **kw):
+    """The energy route's K_eff ([2, 2] float64, on prop_tensor's device) as a differentiable function of the two
+    coefficients prop_tensor ([2], any float dtype, host or device): backward contracts the incoming gradient with
+    dK_dprop, dK_eff / dprop[p] = A_p / |V| (no further solve), and returns it in float64 cast by autograd to
+    prop_tensor's dtype.  The solver rounds prop to float32, so value and derivative are taken AT the float32-rounded
+    prop: a change of prop below its float32 spacing changes neither.  kw: effective_conductivity's (size, dtype,
+    method, rtol, ...).  The derivative is exact only for a converged solve (stationarity), so an unconverged one
+    raises."""
+    if prop_tensor.shape != (2,):
+        raise ValueError("effective_conductivity_torch: prop_tensor must have shape [2], got "
+                         f"{tuple(prop_tensor.shape)}")
+    return _EffectiveConductivity.apply(prop_tensor, phase, kw)

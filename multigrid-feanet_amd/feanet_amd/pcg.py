@@ -292,6 +292,13 @@ class PCGSolver:
         return fx.flux_framed(self.x.data_ptr(), self.dtype, self.device, *self.L0.geom(), phase=img, k0=k0, k1=k1,
                               h=self.mg.size / self.mg.n, fields=fields)
 
+    def energy_forms(self, pair=(0, 1), fields=True):
+        """The energy forms between samples pair[0] and pair[1] of the current iterate x (mixed precision: the fp64
+        x), as MultigridSolver.energy_forms; no host synchronisation."""
+        from . import flux as fx
+        return fx.pair_forms(self.x.data_ptr(), self.dtype, self.device, self.B, self.L0.geom(), pair,
+                             self.mg.flux_image()[0], fields, "PCGSolver.energy_forms")
+
     def residual_norm(self):
         """Per-sample true residual ||(b - K x)[1:-1, 1:-1]||_2 (float64 device tensor [B]), recomputed from x."""
         mg, L0 = self.mg, self.L0

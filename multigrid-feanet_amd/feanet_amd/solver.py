@@ -534,6 +534,17 @@ class MultigridSolver:
         return fx.flux_framed(L0.buf(self._iterate()).data_ptr(), self.dtype, self.device, *L0.geom(), phase=img,
                               k0=k0, k1=k1, h=self.size / self.n, fields=fields)
 
+    def energy_forms(self, pair=(0, 1), fields=True):
+        """The energy forms between samples pair[0] and pair[1] of the current iterate (the buffer solution() reads),
+        split by the phases of flux_image(), as a feanet_amd.flux.EnergyForms with B = 1: A [1, 2, 3], density
+        [1, 3, m, n] or None; no host synchronisation.  The default pair needs batch >= 2; pair=(i, i) is one sample
+        with itself."""
+        from . import flux as fx
+        L0 = self.levels[0]
+        img = self.flux_image()[0]
+        return fx.pair_forms(L0.buf(self._iterate()).data_ptr(), self.dtype, self.device, self.B, L0.geom(), pair, img,
+                             fields, "MultigridSolver.energy_forms")
+
     def residual_norm(self):
         """Per-sample ||(f - K u)[1:-1, 1:-1]||_2 of the current iterate (float64 device tensor [B])."""
         L0 = self.levels[0]
