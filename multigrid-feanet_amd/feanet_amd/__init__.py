@@ -7,6 +7,8 @@
                           energy forms of a pair of fields, split by phase, with their element densities (energy_forms)
   feanet_amd.homogenize   effective_conductivity of a phase image from two load cases (flux or energy route; the
                           energy route with its sensitivities, effective_conductivity_torch for autograd)
+  feanet_amd.periodic     PeriodicPCGSolver: the image as a periodic cell, torus multigrid kernels under projected
+                          conjugate gradients (effective_conductivity(..., bc="periodic"))
   feanet_amd.graphs       GraphCache: eager once, captured as a HIP graph the second time, replayed after
   feanet_amd.mesh_setup  vectorised discretisation tables (pattern maps, stencils)
   FEANet.*                drop-in modules with the reference's names (sibling package)
@@ -22,6 +24,9 @@ def __getattr__(name):
     if name == "PCGSolver":
         from .pcg import PCGSolver
         return PCGSolver
+    if name == "PeriodicPCGSolver":
+        from .periodic import PeriodicPCGSolver
+        return PeriodicPCGSolver
     if name == "element_flux":
         from .flux import element_flux
         return element_flux
@@ -34,7 +39,7 @@ def __getattr__(name):
     if name == "effective_conductivity":
         from .homogenize import effective_conductivity
         return effective_conductivity
-    if name in ("ops", "solver", "pcg", "_lib", "flux", "homogenize"):
+    if name in ("ops", "solver", "pcg", "_lib", "flux", "homogenize", "periodic"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -162,8 +162,22 @@ _ENERGY = {
     "fea_energy_final": "P part, LL per, P sums, I B, P stream",
 }
 _ENERGY_RES = {"fea_energy_parts": LL, "fea_energy_final": I}
+# the torus (periodic cell) multigrid kernels, declared in include/feanet_periodic.h (tests/test_periodic_host.py
+# compares this table with that header), in the form of _FLUX / _FLUX_RES
+_PERIODIC = {
+    "per_sweep": "P u, P f, P out, P pid, LL ldp, P ktab, P omd, I B, I m, I n, I ld, LL bstride, P stream",
+    "per_residual_restrict": "P u, P f, P fc, P pid, LL ldp, P ktab, I B, I m, I n, I ld, LL bstride, I ldc, "
+                             "LL bstridec, P stream",
+    "per_prolong_add": "P ec, P u, I B, I m, I n, I ld, LL bstride, I ldc, LL bstridec, P stream",
+    "per_apply": "P p, P y, P part, P pid, LL ldp, P ktab, I B, I m, I n, I ld, LL bstride, P stream",
+    "per_reduce": "P a, P b, P part, I B, I m, I n, I ld, LL bstride, P stream",
+    "fea_per_parts": "I m, I n, I elem_size",
+    "fea_per_final": "P part, LL per, P sums, I count, P stream",
+}
+_PERIODIC_RES = {"fea_per_parts": LL, "fea_per_final": I}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
 _ENERGY = {name: sig.split(", ") for name, sig in _ENERGY.items()}
+_PERIODIC = {name: sig.split(", ") for name, sig in _PERIODIC.items()}
 _FLUX = {name: sig.split(", ") for name, sig in _FLUX.items()}
 _FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
 _PHASE = {name: sig.split(", ") for name, sig in _PHASE.items()}
@@ -185,6 +199,7 @@ def _names(name):
     if name not in _NAMES:
         sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _FLUX.get(name) or \
             _FLUX.get("fea_" + name) or _ENERGY.get(name) or _ENERGY.get("fea_" + name) or \
+            _PERIODIC.get(name) or _PERIODIC.get("fea_" + name) or \
             _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
@@ -260,6 +275,14 @@ def energy_exported_symbols():
     return names
 
 
+def periodic_exported_symbols():
+    """Every symbol declared in feanet_periodic.h."""
+    names = []
+    for n in _PERIODIC:
+        names += [n] if n.startswith("fea_") else [f"fea_{n}_f32", f"fea_{n}_f64"]
+    return names
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -284,7 +307,7 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = I
-    for table, results in ((_FLUX, _FLUX_RES), (_ENERGY, _ENERGY_RES)):
+    for table, results in ((_FLUX, _FLUX_RES), (_ENERGY, _ENERGY_RES), (_PERIODIC, _PERIODIC_RES)):
         for name, res in results.items():
             fn = sym(name)
             if fn is not None:
@@ -292,6 +315,7 @@ def lib():
                 fn.restype = res
     typed_flux = [(n, sig) for n, sig in _FLUX.items() if n not in _FLUX_RES]
     typed_flux += [(n, sig) for n, sig in _ENERGY.items() if n not in _ENERGY_RES]
+    typed_flux += [(n, sig) for n, sig in _PERIODIC.items() if n not in _PERIODIC_RES]
     for base, sig in list(_SIGS.items()) + list(_FMG.items()) + typed_flux:
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")

@@ -45,14 +45,23 @@ def load_cases(m, n, size, dtype, device):
 
 
 def effective_conductivity(phase, prop=(1, 20), size=2.0, dtype=torch.float64, method="pcg", rtol=1e-10,
-                           max_iters=200, coarsen="stiff", device=None, route="flux", fields=True, **solver_kw):
+                           max_iters=200, coarsen="stiff", device=None, route="flux", fields=True, bc="dirichlet",
+                           **solver_kw):
     """K_eff of the [m, n] element phase image `phase` (host or device; 0 -> prop[0], 1 -> prop[1]) on the rectangle of
     width `size` (h = size / n).  method "pcg": PCGSolver (solver_kw e.g. precond_dtype=torch.float32); "mg":
     MultigridSolver's stationary cycles (all samples run until the slowest is done; a sample whose ||r0|| is at the
     rounding level of the residual counts as solved).  Every sample stops at ||r|| <= rtol ||r0||.  Raises
     RuntimeError if a sample broke down; samples that did not converge in max_iters are reported in flags / converged, not hidden.
     route "flux": K_eff[:, j] = -<q>_j, a HomogenizationResult.  route "energy": K_eff from the energy form of the same
-    two fields with its derivatives, an EnergyHomogenizationResult (fields=False: without the element sensitivity)."""
+    two fields with its derivatives, an EnergyHomogenizationResult (fields=False: without the element sensitivity).
+    bc "dirichlet": the linear fields as Dirichlet data (KUBC, an upper bound).  bc "periodic" (DESIGN §18): the image
+    is a periodic cell, u = X_j + chi_j with a periodic fluctuation chi_j solved by PeriodicPCGSolver (solver_kw: nu,
+    coarse_sweeps, omega, graph, check_every) and evaluated on the unwrapped field; both routes, the same result
+    tuples; method "mg" and precond_dtype are not offered there."""
+    if bc not in ("dirichlet", "periodic"):
+        raise ValueError(f"effective_conductivity: unknown bc {bc!r} ('dirichlet' or 'periodic')")
+    if bc == "periodic":
+        return _periodic(phase, prop, size, dtype, method, rtol, max_iters, coarsen, device, route, fields, solver_kw)
     from .pcg import PCGSolver
     from .solver import MultigridSolver
     if method not in ("pcg", "mg"):
@@ -95,6 +104,32 @@ def effective_conductivity(phase, prop=(1, 20), size=2.0, dtype=torch.float64, m
     if (flags == 2).any():
         raise RuntimeError(f"effective_conductivity: the solve broke down (flags {flags.tolist()}); contrast "
                            f"{prop}, method {method!r}")
+    return _evaluate(s, m, n, h, prop, route, fields, iters, flags)
+
+
+def _periodic(phase, prop, size, dtype, method, rtol, max_iters, coarsen, device, route, fields, solver_kw):
+    """effective_conductivity(bc="periodic")"""
+    from .periodic import PeriodicPCGSolver
+    if method != "pcg":
+        raise ValueError(f"effective_conductivity: bc='periodic' has no method {method!r} (conjugate gradients only)")
+    if "precond_dtype" in solver_kw:
+        raise ValueError("effective_conductivity: bc='periodic' has no mixed precision (precond_dtype)")
+    if route not in ("flux", "energy"):
+        raise ValueError(f"effective_conductivity: unknown route {route!r} ('flux' or 'energy')")
+    if len(phase.shape) != 2:
+        raise ValueError(f"effective_conductivity: phase must be [rows, n], got shape {tuple(phase.shape)}")
+    m, n = (int(v) for v in phase.shape)
+    s = PeriodicPCGSolver(n, rows=m, phase=phase, prop=prop, size=size, dtype=dtype, batch=2, coarsen=coarsen,
+                          device=device, **solver_kw)
+    s.solve(rtol=rtol, max_iters=max_iters)
+    if (s.flags == 2).any():
+        raise RuntimeError(f"effective_conductivity: the solve broke down (flags {s.flags.tolist()}); contrast "
+                           f"{prop}, bc 'periodic'")
+    return _evaluate(s, m, n, size / n, prop, route, fields, s.iterations, s.flags)
+
+
+def _evaluate(s, m, n, h, prop, route, fields, iters, flags):
+    """Both result tuples from a solver that holds the two solved load cases (its flux / energy_forms methods)."""
     res = s.flux(fields=False)
     if route == "energy":
         from .flux import coefficients
