@@ -9,6 +9,8 @@
                           energy route with its sensitivities, effective_conductivity_torch for autograd)
   feanet_amd.periodic     PeriodicPCGSolver: the image as a periodic cell, torus multigrid kernels under projected
                           conjugate gradients (effective_conductivity(..., bc="periodic"))
+  feanet_amd.coef         CoefPeriodicPCGSolver: the periodic cell with one coefficient per element (matrix-free torus
+                          kernels), effective_conductivity_field and its autograd form
   feanet_amd.graphs       GraphCache: eager once, captured as a HIP graph the second time, replayed after
   feanet_amd.mesh_setup  vectorised discretisation tables (pattern maps, stencils)
   FEANet.*                drop-in modules with the reference's names (sibling package)
@@ -27,6 +29,9 @@ def __getattr__(name):
     if name == "PeriodicPCGSolver":
         from .periodic import PeriodicPCGSolver
         return PeriodicPCGSolver
+    if name in ("CoefPeriodicPCGSolver", "effective_conductivity_field", "effective_conductivity_field_torch"):
+        from . import coef
+        return getattr(coef, name)
     if name == "element_flux":
         from .flux import element_flux
         return element_flux
@@ -39,7 +44,7 @@ def __getattr__(name):
     if name == "effective_conductivity":
         from .homogenize import effective_conductivity
         return effective_conductivity
-    if name in ("ops", "solver", "pcg", "_lib", "flux", "homogenize", "periodic"):
+    if name in ("ops", "solver", "pcg", "_lib", "flux", "homogenize", "periodic", "coef"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -175,9 +175,21 @@ _PERIODIC = {
     "fea_per_final": "P part, LL per, P sums, I count, P stream",
 }
 _PERIODIC_RES = {"fea_per_parts": LL, "fea_per_final": I}
+# the element-coefficient-field kernels on the torus, declared in include/feanet_coef.h (tests/test_coef_host.py
+# compares this table with that header), in the form of _PERIODIC / _PERIODIC_RES; every entry point is a typed pair,
+# so the table of dtype-free results is empty (the partial-sum count and the final sum are _PERIODIC's)
+_COEF = {
+    "coef_sweep": "P u, P f, P out, P k, LL ldk, D omega, I B, I m, I n, I ld, LL bstride, P stream",
+    "coef_apply": "P p, P y, P part, P k, LL ldk, I B, I m, I n, I ld, LL bstride, P stream",
+    "coef_residual_restrict": "P u, P f, P fc, P k, LL ldk, I B, I m, I n, I ld, LL bstride, I ldc, LL bstridec, "
+                              "P stream",
+    "coef_coarsen": "P k, LL ldk, P kc, LL ldkc, I m, I n, I rule, P stream",
+}
+_COEF_RES = {}
 # as lists of "TYPE param" fields: len() of an entry is its number of C arguments
 _ENERGY = {name: sig.split(", ") for name, sig in _ENERGY.items()}
 _PERIODIC = {name: sig.split(", ") for name, sig in _PERIODIC.items()}
+_COEF = {name: sig.split(", ") for name, sig in _COEF.items()}
 _FLUX = {name: sig.split(", ") for name, sig in _FLUX.items()}
 _FMG = {name: sig.split(", ") for name, sig in _FMG.items()}
 _PHASE = {name: sig.split(", ") for name, sig in _PHASE.items()}
@@ -200,6 +212,7 @@ def _names(name):
         sig = _SIGS.get(name) or _FMG.get(name) or _PHASE.get("fea_" + name) or _FLUX.get(name) or \
             _FLUX.get("fea_" + name) or _ENERGY.get(name) or _ENERGY.get("fea_" + name) or \
             _PERIODIC.get(name) or _PERIODIC.get("fea_" + name) or \
+            _COEF.get(name) or _COEF.get("fea_" + name) or \
             _EXTRA.get("fea_" + name, ([],))[0]
         names = [p.split()[1] for p in sig]
         if names[-1:] != ["stream"]:
@@ -283,6 +296,14 @@ def periodic_exported_symbols():
     return names
 
 
+def coef_exported_symbols():
+    """Every symbol declared in feanet_coef.h."""
+    names = []
+    for n in _COEF:
+        names += [n] if n.startswith("fea_") else [f"fea_{n}_f32", f"fea_{n}_f64"]
+    return names
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -307,7 +328,8 @@ def lib():
         if fn is not None:
             fn.argtypes = _argtypes(sig)
             fn.restype = I
-    for table, results in ((_FLUX, _FLUX_RES), (_ENERGY, _ENERGY_RES), (_PERIODIC, _PERIODIC_RES)):
+    for table, results in ((_FLUX, _FLUX_RES), (_ENERGY, _ENERGY_RES), (_PERIODIC, _PERIODIC_RES),
+                           (_COEF, _COEF_RES)):
         for name, res in results.items():
             fn = sym(name)
             if fn is not None:
@@ -316,6 +338,7 @@ def lib():
     typed_flux = [(n, sig) for n, sig in _FLUX.items() if n not in _FLUX_RES]
     typed_flux += [(n, sig) for n, sig in _ENERGY.items() if n not in _ENERGY_RES]
     typed_flux += [(n, sig) for n, sig in _PERIODIC.items() if n not in _PERIODIC_RES]
+    typed_flux += [(n, sig) for n, sig in _COEF.items() if n not in _COEF_RES]
     for base, sig in list(_SIGS.items()) + list(_FMG.items()) + typed_flux:
         for suf, S in (("f32", F32), ("f64", F64)):
             fn = sym(f"fea_{base}_{suf}")

@@ -15,7 +15,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libfeanet_hip.so")
 SOURCES = ["generic_ops.hip", "framed_ops.hip", "coarse_tail.hip", "hnet_ops.hip", "mid_ops.hip", "setup_ops.hip",
            "dd_ops.hip", "hjac_tail.hip", "hmid_ops.hip", "pcg_ops.hip", "fmg_ops.hip", "phase_ops.hip",
-           "flux_ops.hip", "energy_ops.hip", "periodic_ops.hip"]
+           "flux_ops.hip", "energy_ops.hip", "periodic_ops.hip", "coef_ops.hip"]
 ARCH = os.environ.get("FEANET_ARCH", "gfx950")
 
 
@@ -29,7 +29,7 @@ def needs_build():
     t = os.path.getmtime(LIB)
     deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     deps += [os.path.join(INCLUDE, h) for h in ("feanet_hip.h", "feanet_fmg.h", "feanet_phase.h", "feanet_flux.h",
-                                                "feanet_energy.h", "feanet_periodic.h")]
+                                                "feanet_energy.h", "feanet_periodic.h", "feanet_coef.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

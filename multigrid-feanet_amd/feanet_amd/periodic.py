@@ -48,11 +48,13 @@ def coarse_shapes(m, n):
     return out
 
 
-def solved_floor(prop, h, m, n, dtype):
+def solved_floor(prop, h, m, n, dtype, kmax=None):
     """||P b|| at or below which a sample starts solved: the rounding level of a residual of fields of size h
-    (effective_conductivity's floor with h for max|u0|)."""
+    (effective_conductivity's floor with h for max|u0|).  kmax: the largest coefficient, where it does not come from
+    prop (feanet_amd.coef)."""
     u_t = 2.0 ** -24 if dtype == torch.float32 else 2.0 ** -53
-    kmax = float(max(np.float32(prop[0]), np.float32(prop[1])))
+    if kmax is None:
+        kmax = float(max(np.float32(prop[0]), np.float32(prop[1])))
     return 22 * u_t * (32.0 * kmax / 6.0) * h * np.sqrt(m * n)
 
 
@@ -118,6 +120,11 @@ class PeriodicPCGSolver:
                 img = ms.coarsen_phase_device(img, k)
             assert tuple(img.shape) == shape
             self.levels.append(_TorusLevel(img, self.B, dtype, self.device))
+        self._allocate()
+
+    def _allocate(self):
+        """The Krylov fields, the partial sums and the per-sample scalars, once self.levels stands."""
+        m, n = self.m, self.n
         L0 = self.levels[0]
         self.r = L0.f  # the preconditioner's right-hand side buffer is the residual
         self._x, self.p, self.y = (torch.zeros_like(L0.f) for _ in range(3))
@@ -147,6 +154,15 @@ class PeriodicPCGSolver:
                    pid=L.pid.data_ptr(), ldp=L.ldp, ktab=self.ktab.data_ptr(), omd=self.omd.data_ptr(), B=self.B,
                    **L.geom())
 
+    def _residual_restrict(self, L, C, u):
+        """C.f = R (L.f - K u)"""
+        self._call("per_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), pid=L.pid.data_ptr(),
+                   ldp=L.ldp, ktab=self.ktab.data_ptr(), B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
+
+    def _floor(self):
+        """solved_floor of this solver's operator"""
+        return solved_floor(self.prop, self.h, self.m, self.n, self.dtype)
+
     def _sweeps(self, L, u, count):
         """count sweeps from u (None: the zero guess), ping-pong between L.a and L.b -> the buffer of the result"""
         for _ in range(count):
@@ -162,8 +178,7 @@ class PeriodicPCGSolver:
             return self._sweeps(L, None, self.coarse_sweeps)
         C = self.levels[l + 1]
         u = self._sweeps(L, None, self.nu)
-        self._call("per_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), pid=L.pid.data_ptr(),
-                   ldp=L.ldp, ktab=self.ktab.data_ptr(), B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
+        self._residual_restrict(L, C, u)
         ec = self._cycle(l + 1)
         self._call("per_prolong_add", ec=ec.data_ptr(), u=u.data_ptr(), B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
         return self._sweeps(L, u, self.nu)
@@ -260,7 +275,7 @@ class PeriodicPCGSolver:
         self.rr0.copy_(torch.sqrt(self._reduce(self.r, self.r)))
         self.rn.copy_(self.rr0)
         self.thresh.copy_(self.rr0 * float(rtol))
-        self.flag.copy_((self.rr0 <= solved_floor(self.prop, self.h, m, n, self.dtype)).to(torch.int64))
+        self.flag.copy_((self.rr0 <= self._floor()).to(torch.int64))
         self.rz_old.fill_(float("inf"))
         self.iters.zero_()
         self.hist[0] = self.rr0
