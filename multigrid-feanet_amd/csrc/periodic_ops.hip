@@ -8,23 +8,14 @@
 //   prolong_add        u += R^T ec
 //   final              one workgroup per quantity sums its partials in a fixed order
 //
-// Torus layout: [B, m, ld] without a ghost ring; every index wraps.  sweep, apply and reduce use the strip x row-march
-// decomposition of the framed kernels (framed_strip.h): a wave owns a strip of 64 * VEC node columns and a task of rb
-// rows, a lane owns VEC columns (one 16-byte load per row), three node rows sit in a register window that marches
-// down and the row after the next is loaded before the arithmetic.  Left and right neighbours come by DPP inside the
-// wave; the columns next to the strip (lane 0: column cl - 1, or n - 1 at column 0; lane 63: column cl + VEC) and
-// column 0, the right neighbour of column n - 1 wherever that column lies in the strip, are explicit loads.  Rows wrap
-// in the row pointer.  On a 2 x k level the row above and the row below are the same row, and on an m x 2 level the
-// left and the right neighbour are the same node: the window then simply holds the node twice and both taps are added.
-// The stencil is kapply's two-material form (all nine weights from the node's own table row, mirrored taps), the sweep
-// is jacobi(): the expressions of the framed kernels, written once.  The row tasks are those ONE sample gets, so a
-// sample's partial sums are the same bits in any batch.  Pad columns are loaded with their vector but every value
-// taken from them is selected out; nothing outside the m x n nodes is written.
+// Layout, decomposition, row helpers, task decoding and the host checks: torus_strip.h.  What is this file's own: a
+// node's nine weights are its own row of the stencil table in LDS (kapply's two-material form, mirrored taps), found
+// through the pattern map, and the sweep is jacobi(): the expressions of the framed kernels, written once.
 // residual_restrict and prolong_add take one thread per coarse / fine node with modulo indexing at every size (the
 // first version: the coarse levels are launch-bound, the fine ones re-read their neighbourhood from the caches).  A
 // strip form of residual_restrict (the residual rows of a coarse row in registers, one residual per row by DPP) was
 // measured at 4096^2: 56.0 us against 97.5 in fp32, but 194.5 against 134.9 in fp64, at 158 VGPRs.
-#include "framed_strip.h"
+#include "torus_strip.h"
 #include "feanet_periodic.h"
 
 namespace fea {
@@ -50,43 +41,6 @@ struct PerArgs {
   int B;  // the one-thread-per-node kernels' batch bound
 };
 
-// one node row of a lane: x = own columns, hl / hr = the strip's outer neighbours (lanes 0 / 63), w0 = column 0
-template <typename T, int V>
-struct PerRaw {
-  T x[V];
-  T hl, hr, w0;
-};
-
-template <typename T, int V>
-__device__ __forceinline__ PerRaw<T, V> per_load(const T* __restrict__ rp, int cl, int cL, int n, int lane) {
-  PerRaw<T, V> r;
-#pragma unroll
-  for (int k = 0; k < V; ++k) r.x[k] = T(0);
-  if (cl < n) vload<T, V>(rp + cl, r.x);  // columns cl .. cl+V-1 <= ld-1 (ld a multiple of V)
-  r.hl = T(0);
-  r.hr = T(0);
-  if (lane == 0) r.hl = rp[cL];                           // exec-masked scalar loads
-  if (lane == kWave - 1 && cl + V < n) r.hr = rp[cl + V];
-  r.w0 = rp[0];
-  return r;
-}
-
-// the window row: a[0] = left of the first own column, a[1 .. V] own, a[V+1] = right of the last own column; the right
-// neighbour of column n-1 is column 0
-template <typename T, int V>
-__device__ __forceinline__ Row<T, V> per_window(const PerRaw<T, V>& r, int cl, int n) {
-  Row<T, V> w;
-#pragma unroll
-  for (int k = 0; k < V; ++k) w.a[k + 1] = r.x[k];
-  w.a[0] = shr1(r.x[V - 1], r.hl);
-  w.a[V + 1] = shl1(r.x[0], r.hr);
-  w.a[V + 2] = T(0);
-#pragma unroll
-  for (int k = 0; k < V; ++k)
-    if (cl + k == n - 1) w.a[k + 2] = r.w0;
-  return w;
-}
-
 // the own columns' table-row byte offsets (pad bytes are clamped to a row of the table; their results are masked)
 template <typename T, int V>
 __device__ __forceinline__ PRow<V> per_pids(const uint8_t* __restrict__ pp, int cl, int n) {
@@ -102,36 +56,6 @@ __device__ __forceinline__ PRow<V> per_pids(const uint8_t* __restrict__ pp, int 
   return p;
 }
 
-template <typename T, int V>
-__device__ __forceinline__ void per_store(T* p, const T (&o)[V], int cl, int n) {
-  if (cl + V <= n) {
-    vstore<T, V, false>(p, o);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k)
-      if (cl + k < n) p[k] = o[k];
-  }
-}
-
-struct PerTask {
-  int b, s, t, r0, r1, cl, cL, lane;
-};
-template <typename T>
-__device__ __forceinline__ PerTask per_task(const TaskId& id, int m, int n, int rb) {
-  PerTask k;
-  k.b = id.b;
-  k.s = id.s;
-  k.t = id.t;
-  k.lane = lane_id();
-  k.r0 = id.t * rb;
-  k.r1 = min(k.r0 + rb, m);
-  k.cl = id.s * Frame<T>::SW + Frame<T>::VEC * k.lane;
-  k.cL = (k.cl == 0 ? n : k.cl) - 1;  // only lane 0 reads it: cl = c0 < n there
-  return k;
-}
-
-__device__ __forceinline__ int wrap_row(int r, int m) { return r < 0 ? r + m : (r >= m ? r - m : r); }
-
 // SWEEP: out = u + omd (f - K u) (ZERO: omd f); else y = K u, PART: with the partials of u . y and of sum y
 template <typename T, bool SWEEP, bool ZERO, bool PART>
 __global__ __launch_bounds__(256) void k_per_stencil(PerArgs<T> g) {
@@ -142,7 +66,7 @@ __global__ __launch_bounds__(256) void k_per_stencil(PerArgs<T> g) {
   __syncthreads();
   const TaskId id = decode_task(g.nstrips, g.ntr);
   if (!id.valid) return;
-  const PerTask k = per_task<T>(id, g.m, g.n, g.rb);
+  const TorusTask k = torus_task<T>(id, g.m, g.n, g.rb);
   const int m = g.m, n = g.n, ld = g.ld, cl = k.cl;
   const T ks[9] = {};
   T* __restrict__ ob = g.out + (long long)k.b * g.bs;
@@ -157,24 +81,24 @@ __global__ __launch_bounds__(256) void k_per_stencil(PerArgs<T> g) {
       const PRow<V> pb = per_pids<T, V>(g.pid + (long long)r * g.ldp, cl, n);
 #pragma unroll
       for (int j = 0; j < V; ++j) o[j] = tabv(tab, pb.a[j + 1], 9) * fv[j];
-      if (cl < n) per_store<T, V>(ob + (long long)r * ld + cl, o, cl, n);
+      if (cl < n) torus_store<T, V>(ob + (long long)r * ld + cl, o, cl, n);
     }
   } else {
     const T* __restrict__ ub = g.u + (long long)k.b * g.bs;
-    auto rowp = [&](int r) { return ub + (long long)wrap_row(r, m) * ld; };
-    Row<T, V> wa = per_window<T, V>(per_load<T, V>(rowp(k.r0 - 1), cl, k.cL, n, k.lane), cl, n);
-    Row<T, V> wb = per_window<T, V>(per_load<T, V>(rowp(k.r0), cl, k.cL, n, k.lane), cl, n);
-    PerRaw<T, V> rc = per_load<T, V>(rowp(k.r0 + 1), cl, k.cL, n, k.lane);
+    auto rowp = [&](int r) { return ub + (long long)torus_wrap(r, m) * ld; };
+    Row<T, V> wa = torus_window<T, V>(torus_load<T, V>(rowp(k.r0 - 1), cl, k.cL, n, k.lane), cl, n);
+    Row<T, V> wb = torus_window<T, V>(torus_load<T, V>(rowp(k.r0), cl, k.cL, n, k.lane), cl, n);
+    TorusRaw<T, V> rc = torus_load<T, V>(rowp(k.r0 + 1), cl, k.cL, n, k.lane);
     for (int r = k.r0; r < k.r1; ++r) {
       // (behind the task's last row: the row is loaded again and never used)
-      const PerRaw<T, V> rd = per_load<T, V>(rowp(min(r + 2, k.r1)), cl, k.cL, n, k.lane);
+      const TorusRaw<T, V> rd = torus_load<T, V>(rowp(min(r + 2, k.r1)), cl, k.cL, n, k.lane);
       T fv[V], o[V];
 #pragma unroll
       for (int j = 0; j < V; ++j) fv[j] = T(0);
       if constexpr (SWEEP)
         if (cl < n) vload<T, V>(g.f + (long long)k.b * g.bs + (long long)r * ld + cl, fv);
       const PRow<V> pb = per_pids<T, V>(g.pid + (long long)r * g.ldp, cl, n);
-      const Row<T, V> wc = per_window<T, V>(rc, cl, n);
+      const Row<T, V> wc = torus_window<T, V>(rc, cl, n);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         if constexpr (SWEEP) o[j] = jacobi<T, V, true>(wa, wb, wc, pb, pb, pb, j, fv[j], ks, T(0), tab);
@@ -185,7 +109,7 @@ __global__ __launch_bounds__(256) void k_per_stencil(PerArgs<T> g) {
           s1 += in ? (double)o[j] : 0.0;
         }
       }
-      if (cl < n) per_store<T, V>(ob + (long long)r * ld + cl, o, cl, n);
+      if (cl < n) torus_store<T, V>(ob + (long long)r * ld + cl, o, cl, n);
       wa = wb;
       wb = wc;
       rc = rd;
@@ -209,7 +133,7 @@ __global__ __launch_bounds__(256) void k_per_reduce(PerArgs<T> g) {
   constexpr int V = F::VEC;
   const TaskId id = decode_task(g.nstrips, g.ntr);
   if (!id.valid) return;
-  const PerTask k = per_task<T>(id, g.m, g.n, g.rb);
+  const TorusTask k = torus_task<T>(id, g.m, g.n, g.rb);
   const int n = g.n, cl = k.cl;
   double s = 0.0;
   for (int r = k.r0; r < k.r1; ++r) {
@@ -260,28 +184,21 @@ __global__ __launch_bounds__(256) void k_per_residual_restrict(PerArgs<T> g) {
   __shared__ T tab[kPerTab * kTabStride];
   load_tables<T>(tab, g.ktab, (const T*)nullptr, kPerTab, (T*)nullptr, (const T*)nullptr, 0);
   __syncthreads();
-  const long long per_b = (long long)g.mc * g.nc;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long b = i / per_b;
-  if (b >= g.B) return;
-  const long long rem = i - b * per_b;
-  const int I = (int)(rem / g.nc), J = (int)(rem - (long long)I * g.nc);
-  const T* __restrict__ ub = ZERO ? nullptr : g.u + b * g.bs;
-  const T* __restrict__ fb = g.f + b * g.bs;
-  const int r1 = 2 * I, c1 = 2 * J;
-  const int r0 = r1 == 0 ? g.m - 1 : r1 - 1, r2 = r1 + 1;  // m, n even: 2 I + 1 <= m - 1
-  const int c0 = c1 == 0 ? g.n - 1 : c1 - 1, c2 = c1 + 1;
+  TorusCoarse k;
+  if (!torus_coarse(g, k)) return;
+  const T* __restrict__ ub = ZERO ? nullptr : g.u + k.b * g.bs;
+  const T* __restrict__ fb = g.f + k.b * g.bs;
   const T q = T(0.25), h = T(0.5);
-  T acc = q * per_residual_at<T, ZERO>(g, ub, fb, tab, r0, c0);
-  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, r0, c1);
-  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, r0, c2);
-  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, r1, c0);
-  acc += per_residual_at<T, ZERO>(g, ub, fb, tab, r1, c1);
-  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, r1, c2);
-  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, r2, c0);
-  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, r2, c1);
-  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, r2, c2);
-  g.out[b * g.bsc + (long long)I * g.ldc + J] = acc;
+  T acc = q * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r0, k.c0);
+  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r0, k.c1);
+  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r0, k.c2);
+  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r1, k.c0);
+  acc += per_residual_at<T, ZERO>(g, ub, fb, tab, k.r1, k.c1);
+  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r1, k.c2);
+  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r2, k.c0);
+  acc += h * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r2, k.c1);
+  acc += q * per_residual_at<T, ZERO>(g, ub, fb, tab, k.r2, k.c2);
+  g.out[k.b * g.bsc + (long long)k.I * g.ldc + k.J] = acc;
 }
 
 // u += R^T ec: one thread per fine node; ec = g.u (coarse), u = g.out (fine)
@@ -323,58 +240,34 @@ __global__ __launch_bounds__(256) void k_per_final(const double* __restrict__ pa
 
 }  // namespace fea
 
-static inline bool per_dim_ok(int n) { return n >= 1 && n <= (1 << 20); }
-
-// strips over the node columns 0 .. n-1, row tasks of the height ONE sample gets
 template <typename T>
-static void per_geom(int m, int n, int& nstrips, int& rb, int& ntr) {
-  nstrips = div_up(n, Frame<T>::SW);
-  rb = pick_rb(1, nstrips, m);
-  ntr = div_up(m, rb);
-}
-
-template <typename T>
-static bool per_layout_ok(int m, int n, int ld, long long bs) {
-  constexpr int V = Frame<T>::VEC;
-  return per_dim_ok(m) && per_dim_ok(n) && ld >= n && ld % V == 0 && bs >= (long long)m * ld && bs % V == 0;
-}
-static inline bool per_aligned(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+static bool per_layout_ok(int m, int n, int ld, long long bs) { return torus_layout_ok<T>(m, n, ld, bs, 1); }
 template <typename T>
 static bool per_pid_ok(const uint8_t* pid, long long ldp, int n) {
   constexpr int V = Frame<T>::VEC;
   return pid && (uintptr_t)pid % 4 == 0 && ldp % 4 == 0 && ldp >= (long long)div_up(n, V) * V;
 }
-template <typename T>
-static bool per_overlap(const T* a, const T* b, int B, long long bs) {
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)B * bs * sizeof(T);
-  const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)B * bs * sizeof(T);
-  return a0 < b1 && b0 < a1;
-}
 
 template <typename T>
 static PerArgs<T> per_args(int m, int n, int ld, long long bs) {
   PerArgs<T> g{};
-  g.m = m; g.n = n; g.ld = ld; g.bs = bs;
-  per_geom<T>(m, n, g.nstrips, g.rb, g.ntr);
-  g.per = (long long)g.nstrips * g.ntr;
+  torus_geom<T>(g, m, n, ld, bs);
   return g;
 }
 
 extern "C" long long fea_per_parts(int m, int n, int elem_size) {
-  if (!per_dim_ok(m) || !per_dim_ok(n) || (elem_size != 4 && elem_size != 8)) return -1;
-  int ns, rb, ntr;
-  if (elem_size == 8) per_geom<double>(m, n, ns, rb, ntr);
-  else per_geom<float>(m, n, ns, rb, ntr);
-  return (long long)ns * ntr;
+  if (!torus_dim_ok(m, 1) || !torus_dim_ok(n, 1) || (elem_size != 4 && elem_size != 8)) return -1;
+  return elem_size == 8 ? per_args<double>(m, n, 0, 0).per : per_args<float>(m, n, 0, 0).per;
 }
 
 template <typename T>
 static int per_sweep(const T* u, const T* f, T* out, const uint8_t* pid, long long ldp, const T* ktab, const T* omd,
                      int B, int m, int n, int ld, long long bs, void* stream) {
-  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !per_aligned(f) || !per_aligned(out) || (u && !per_aligned(u)) ||
-      !per_pid_ok<T>(pid, ldp, n) || !ktab || !omd)
+  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !torus_aligned(f) || !torus_aligned(out) ||
+      (u && !torus_aligned(u)) || !per_pid_ok<T>(pid, ldp, n) || !ktab || !omd)
     return FEA_EINVAL;
-  if ((u && per_overlap(u, out, B, bs)) || per_overlap(f, out, B, bs)) return FEA_EINVAL;
+  const long long N = (long long)B * bs;
+  if ((u && torus_overlap(u, N, out, N)) || torus_overlap(f, N, out, N)) return FEA_EINVAL;
   PerArgs<T> g = per_args<T>(m, n, ld, bs);
   g.u = u; g.f = f; g.out = out; g.pid = pid; g.ldp = ldp; g.ktab = ktab; g.omd = omd;
   const dim3 grid = mg_grid(B, g.ntr, g.nstrips);
@@ -386,8 +279,9 @@ static int per_sweep(const T* u, const T* f, T* out, const uint8_t* pid, long lo
 template <typename T>
 static int per_apply(const T* p, T* y, double* part, const uint8_t* pid, long long ldp, const T* ktab, int B, int m,
                      int n, int ld, long long bs, void* stream) {
-  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !per_aligned(p) || !per_aligned(y) || !per_pid_ok<T>(pid, ldp, n) ||
-      !ktab || per_overlap(p, y, B, bs))
+  const long long N = (long long)B * bs;
+  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !torus_aligned(p) || !torus_aligned(y) ||
+      !per_pid_ok<T>(pid, ldp, n) || !ktab || torus_overlap(p, N, y, N))
     return FEA_EINVAL;
   PerArgs<T> g = per_args<T>(m, n, ld, bs);
   g.u = p; g.out = y; g.part = part; g.pid = pid; g.ldp = ldp; g.ktab = ktab;
@@ -399,7 +293,7 @@ static int per_apply(const T* p, T* y, double* part, const uint8_t* pid, long lo
 
 template <typename T>
 static int per_reduce(const T* a, const T* b, double* part, int B, int m, int n, int ld, long long bs, void* stream) {
-  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !per_aligned(a) || (b && !per_aligned(b)) || !part)
+  if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || !torus_aligned(a) || (b && !torus_aligned(b)) || !part)
     return FEA_EINVAL;
   PerArgs<T> g = per_args<T>(m, n, ld, bs);
   g.u = a; g.f = b; g.part = part;
@@ -409,25 +303,17 @@ static int per_reduce(const T* a, const T* b, double* part, int B, int m, int n,
   return launch_status();
 }
 
-// one thread per node of B samples of `nodes` nodes
-static inline bool per_node_grid(int B, long long nodes, dim3& grid) {
-  const long long blocks = (B * nodes + 255) / 256;
-  if (blocks > 0x7fffffffll) return false;
-  grid = dim3((unsigned)blocks);
-  return true;
-}
-
 template <typename T>
 static int per_residual_restrict(const T* u, const T* f, T* fc, const uint8_t* pid, long long ldp, const T* ktab, int B,
                                  int m, int n, int ld, long long bs, int ldc, long long bsc, void* stream) {
   if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || (m & 1) || (n & 1) || !per_layout_ok<T>(m / 2, n / 2, ldc, bsc) ||
-      !per_aligned(f) || !per_aligned(fc) || (u && !per_aligned(u)) || !per_pid_ok<T>(pid, ldp, n) || !ktab)
+      !torus_aligned(f) || !torus_aligned(fc) || (u && !torus_aligned(u)) || !per_pid_ok<T>(pid, ldp, n) || !ktab)
     return FEA_EINVAL;
   PerArgs<T> g = per_args<T>(m, n, ld, bs);
   g.u = u; g.f = f; g.out = fc; g.pid = pid; g.ldp = ldp; g.ktab = ktab;
   g.mc = m / 2; g.nc = n / 2; g.ldc = ldc; g.bsc = bsc;
   dim3 grid;
-  if (!per_node_grid(B, (long long)g.mc * g.nc, grid)) return FEA_EINVAL;
+  if (!torus_node_grid(B, (long long)g.mc * g.nc, grid)) return FEA_EINVAL;
   g.B = B;
   if (u) hipLaunchKernelGGL((k_per_residual_restrict<T, false>), grid, dim3(256), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL((k_per_residual_restrict<T, true>), grid, dim3(256), 0, (hipStream_t)stream, g);
@@ -438,13 +324,13 @@ template <typename T>
 static int per_prolong_add(const T* ec, T* u, int B, int m, int n, int ld, long long bs, int ldc, long long bsc,
                            void* stream) {
   if (B < 1 || !per_layout_ok<T>(m, n, ld, bs) || (m & 1) || (n & 1) || !per_layout_ok<T>(m / 2, n / 2, ldc, bsc) ||
-      !per_aligned(ec) || !per_aligned(u))
+      !torus_aligned(ec) || !torus_aligned(u))
     return FEA_EINVAL;
   PerArgs<T> g = per_args<T>(m, n, ld, bs);
   g.u = ec; g.out = u;
   g.mc = m / 2; g.nc = n / 2; g.ldc = ldc; g.bsc = bsc;
   dim3 grid;
-  if (!per_node_grid(B, (long long)m * n, grid)) return FEA_EINVAL;
+  if (!torus_node_grid(B, (long long)m * n, grid)) return FEA_EINVAL;
   g.B = B;
   hipLaunchKernelGGL((k_per_prolong_add<T>), grid, dim3(256), 0, (hipStream_t)stream, g);
   return launch_status();

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .flux import EnergyForms, FluxResult
 from .homogenize import EnergyHomogenizationResult, HomogenizationResult
-from .periodic import PeriodicPCGSolver, coarse_shapes, solved_floor
+from .periodic import PeriodicPCGSolver
 
 RULES = {"arithmetic": 0, "harmonic": 1, "geometric": 2}  # FEA_COEF_ARITHMETIC, _HARMONIC, _GEOMETRIC
 
@@ -39,24 +39,6 @@ def check_field(k):
     return t
 
 
-class _CoefLevel:
-    def __init__(self, m, n, B, dtype, device):
-        self.m, self.n = int(m), int(n)
-        self.esz = 4 if dtype == torch.float32 else 8
-        vec = 16 // self.esz
-        self.ld = -(-self.n // vec) * vec
-        self.bs = self.m * self.ld
-        self.ldk = self.ld  # the pitch of the element fields of the flux and energy kernels too
-        self.k = torch.ones((self.m, self.ldk), dtype=dtype, device=device)
-        self.f, self.a, self.b = (torch.zeros((B, self.m, self.ld), dtype=dtype, device=device) for _ in range(3))
-
-    def geom(self):
-        return dict(m=self.m, n=self.n, ld=self.ld, bstride=self.bs)
-
-    def field(self):
-        return dict(k=self.k.data_ptr(), ldk=self.ldk)
-
-
 class CoefPeriodicPCGSolver(PeriodicPCGSolver):
     """PeriodicPCGSolver for an [rows, n] element coefficient field `coef` (host or device, any real dtype; rounded to
     the solver's dtype): conjugate gradients on the projected operator, preconditioned by one V(nu, nu) cycle from a
@@ -67,46 +49,29 @@ class CoefPeriodicPCGSolver(PeriodicPCGSolver):
 
     def __init__(self, n, rows=None, coef=None, size=2.0, dtype=torch.float64, batch=2, nu=1, coarse_sweeps=2,
                  coarsen="geometric", omega=2.0 / 3.0, graph=True, check_every=8, device=None):
-        if dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"CoefPeriodicPCGSolver: unsupported dtype {dtype} (float32/float64 only)")
         if coef is None:
             raise ValueError("CoefPeriodicPCGSolver: give the element coefficient field `coef`")
         if coarsen not in RULES:
             raise ValueError(f"CoefPeriodicPCGSolver: unknown coarsen {coarsen!r} ({', '.join(RULES)})")
         field = check_field(coef)
-        m = int(n if rows is None else rows)
-        n = int(n)
-        if tuple(int(v) for v in field.shape) != (m, n):
-            raise ValueError(f"CoefPeriodicPCGSolver: coef is {tuple(field.shape)}, the cell has {m} x {n} elements")
-        if int(nu) < 1 or int(coarse_sweeps) < 1 or int(batch) < 1 or int(check_every) < 1:
-            raise ValueError("CoefPeriodicPCGSolver: nu, coarse_sweeps, batch and check_every must be at least 1")
-        if not torch.cuda.is_available():
-            raise RuntimeError("CoefPeriodicPCGSolver needs the MI355X (there is no CPU fallback for the HIP path)")
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        _lib.lib()
-        self.m, self.n, self.B, self.dtype = m, n, int(batch), dtype
-        self.size, self.h, self.omega = float(size), float(size) / n, float(omega)
-        self.nu, self.coarse_sweeps = int(nu), int(coarse_sweeps)
-        self.use_graph, self.check_every = bool(graph), int(check_every)
+        self._common(n, rows, "coef", field.shape, size, dtype, batch, nu, coarse_sweeps, omega, graph, check_every,
+                     device)
         self.coarsen = coarsen
+        self.prop = None  # there are no two materials here
         k0 = field.to(self.device).to(dtype)
         if not bool((torch.isfinite(k0) & (k0 > 0)).all()):
             raise ValueError(f"CoefPeriodicPCGSolver: a coefficient is not positive and finite once rounded to {dtype}")
-        self.levels = []
-        for i, (lm, ln) in enumerate(coarse_shapes(m, n)):
-            L = _CoefLevel(lm, ln, self.B, dtype, self.device)
-            if i == 0:
-                L.k[:, :n] = k0
+        self.kmax = float(k0.max())
+        F = None
+        for L in self.levels:
+            L.ldk = L.ld  # the pitch of the element fields of the flux and energy kernels too
+            L.k = torch.ones((L.m, L.ldk), dtype=dtype, device=self.device)
+            if F is None:
+                L.k[:, :self.n] = k0
             else:
-                F = self.levels[-1]
                 _lib.call("coef_coarsen", dtype, F.k.data_ptr(), F.ldk, L.k.data_ptr(), L.ldk, F.m, F.n,
                           RULES[coarsen], self._stream())
-            self.levels.append(L)
-        self.kmax = float(k0.max())
-        self.prop = None  # there are no two materials here
-        self._allocate()
+            F = L
 
     @property
     def coef(self):
@@ -114,25 +79,19 @@ class CoefPeriodicPCGSolver(PeriodicPCGSolver):
         return self.levels[0].k[:, :self.n]
 
     # ------------------------------------------------------------------ launches
+    def _field(self, L):
+        return dict(k=L.k.data_ptr(), ldk=L.ldk)
+
     def _sweep(self, L, u, out):
         self._call("coef_sweep", u=None if u is None else u.data_ptr(), f=L.f.data_ptr(), out=out.data_ptr(),
-                   **L.field(), omega=self.omega, B=self.B, **L.geom())
+                   **self._field(L), omega=self.omega, B=self.B, **L.geom())
 
     def _residual_restrict(self, L, C, u):
-        self._call("coef_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), **L.field(),
+        self._call("coef_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), **self._field(L),
                    B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
 
-    def _floor(self):
-        return solved_floor(None, self.h, self.m, self.n, self.dtype, kmax=self.kmax)
-
-    def apply(self, p, y, sums=False):
-        """y = K p on torus buffers; sums: also (p . y, sum y) per sample as a [B, 2] float64 view."""
-        L0 = self.levels[0]
-        self._call("coef_apply", p=p.data_ptr(), y=y.data_ptr(), part=self.part.data_ptr() if sums else None,
-                   **L0.field(), B=self.B, **L0.geom())
-        if sums:
-            self._final(2 * self.B)
-            return self.sums.view(self.B, 2)
+    def _apply(self, L, p, y, part):
+        self._call("coef_apply", p=p.data_ptr(), y=y.data_ptr(), part=part, **self._field(L), B=self.B, **L.geom())
 
     def load_case_rhs(self):
         """[2, m, n] float64: b_0 = (h / 2) ((k_SW + k_SE) - (k_NW + k_NE)), b_1 = (h / 2) ((k_NE + k_SE) - (k_NW +
@@ -149,11 +108,6 @@ class CoefPeriodicPCGSolver(PeriodicPCGSolver):
         self._call("per_reduce", a=ptr, b=L0.k.data_ptr(), part=self.part.data_ptr(), B=1, **L0.geom())
         self._final(1)
         return self.sums[0].clone()
-
-    def _framed(self):
-        from . import flux as fx
-        framed, B, H, W, ld, bs = fx._framed_copy(self.unwrapped(), "u")
-        return framed, (B, H, W, ld, bs)
 
     def _forms(self, framed, geom, pair, who):
         """(the three sums of k d over the elements, the densities [1, 3, m, n]) of samples pair[0], pair[1]"""

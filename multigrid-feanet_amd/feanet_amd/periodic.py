@@ -48,27 +48,23 @@ def coarse_shapes(m, n):
     return out
 
 
-def solved_floor(prop, h, m, n, dtype, kmax=None):
-    """||P b|| at or below which a sample starts solved: the rounding level of a residual of fields of size h
-    (effective_conductivity's floor with h for max|u0|).  kmax: the largest coefficient, where it does not come from
-    prop (feanet_amd.coef)."""
+def solved_floor(kmax, h, m, n, dtype):
+    """||P b|| at or below which a sample starts solved: the rounding level of a residual of fields of size h of an
+    operator whose largest coefficient is kmax (effective_conductivity's floor with h for max|u0|)."""
     u_t = 2.0 ** -24 if dtype == torch.float32 else 2.0 ** -53
-    if kmax is None:
-        kmax = float(max(np.float32(prop[0]), np.float32(prop[1])))
     return 22 * u_t * (32.0 * kmax / 6.0) * h * np.sqrt(m * n)
 
 
 class _TorusLevel:
-    def __init__(self, image, B, dtype, device):
-        self.m, self.n = (int(v) for v in image.shape)
+    """The geometry and the f / a / b buffers of one level; the solver that owns it attaches its operator's data
+    (PeriodicPCGSolver: image, pid, ldp; feanet_amd.coef: k, ldk)."""
+
+    def __init__(self, m, n, B, dtype, device):
+        self.m, self.n = int(m), int(n)
         self.esz = 4 if dtype == torch.float32 else 8
         vec = 16 // self.esz
         self.ld = -(-self.n // vec) * vec
         self.bs = self.m * self.ld
-        self.ldp = -(-self.n // 16) * 16
-        self.image = image
-        self.pid = torch.zeros((self.m, self.ldp), dtype=torch.uint8, device=device)
-        self.pid[:, :self.n] = wrapped_pattern_map(image)
         self.f, self.a, self.b = (torch.zeros((B, self.m, self.ld), dtype=dtype, device=device) for _ in range(3))
 
     def geom(self):
@@ -84,28 +80,14 @@ class PeriodicPCGSolver:
 
     def __init__(self, n, rows=None, phase=None, prop=(1, 20), size=2.0, dtype=torch.float64, batch=2, nu=1,
                  coarse_sweeps=2, coarsen="stiff", omega=2.0 / 3.0, graph=True, check_every=8, device=None):
-        if dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"PeriodicPCGSolver: unsupported dtype {dtype} (float32/float64 only)")
         if phase is None:
             raise ValueError("PeriodicPCGSolver: give the element phase image `phase`")
         if len(phase.shape) != 2:
             raise ValueError(f"PeriodicPCGSolver: phase must be [rows, n], got shape {tuple(phase.shape)}")
-        m = int(n if rows is None else rows)
-        n = int(n)
-        if tuple(int(v) for v in phase.shape) != (m, n):
-            raise ValueError(f"PeriodicPCGSolver: phase is {tuple(phase.shape)}, the cell has {m} x {n} elements")
-        if int(nu) < 1 or int(coarse_sweeps) < 1 or int(batch) < 1 or int(check_every) < 1:
-            raise ValueError("PeriodicPCGSolver: nu, coarse_sweeps, batch and check_every must be at least 1")
-        if not torch.cuda.is_available():
-            raise RuntimeError("PeriodicPCGSolver needs the MI355X (there is no CPU fallback for the HIP path)")
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        _lib.lib()
-        self.m, self.n, self.B, self.dtype = m, n, int(batch), dtype
-        self.size, self.prop, self.h = float(size), tuple(prop), float(size) / n
-        self.nu, self.coarse_sweeps = int(nu), int(coarse_sweeps)
-        self.use_graph, self.check_every = bool(graph), int(check_every)
+        self._common(n, rows, "phase", phase.shape, size, dtype, batch, nu, coarse_sweeps, omega, graph, check_every,
+                     device)
+        self.prop = tuple(prop)
+        self.kmax = float(max(np.float32(prop[0]), np.float32(prop[1])))
         npdt = np.float32 if dtype == torch.float32 else np.float64
         ktab = ms.stencil_table(self.prop)
         self.ktab_np = ktab
@@ -114,17 +96,38 @@ class PeriodicPCGSolver:
         self.bt = torch.from_numpy(load_table(ktab, self.h)).to(self.device)
         img = ms._phase_tensor(phase, self.device)
         k = ms.phase_min_count(self.prop, coarsen)
-        self.levels = []
-        for i, shape in enumerate(coarse_shapes(m, n)):
+        for i, L in enumerate(self.levels):
             if i:
                 img = ms.coarsen_phase_device(img, k)
-            assert tuple(img.shape) == shape
-            self.levels.append(_TorusLevel(img, self.B, dtype, self.device))
-        self._allocate()
+            assert tuple(img.shape) == (L.m, L.n)
+            L.image, L.ldp = img, -(-L.n // 16) * 16
+            L.pid = torch.zeros((L.m, L.ldp), dtype=torch.uint8, device=self.device)
+            L.pid[:, :L.n] = wrapped_pattern_map(img)
 
-    def _allocate(self):
-        """The Krylov fields, the partial sums and the per-sample scalars, once self.levels stands."""
-        m, n = self.m, self.n
+    def _common(self, n, rows, what, shape, size, dtype, batch, nu, coarse_sweeps, omega, graph, check_every, device):
+        """What every solver on the torus layout checks and holds: the cell against the [rows, n] input `what` of
+        shape `shape`, the device, the library, the scalars, the levels without their operator, the Krylov fields,
+        the partial sums and the per-sample scalars."""
+        name = type(self).__name__
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{name}: unsupported dtype {dtype} (float32/float64 only)")
+        m = int(n if rows is None else rows)
+        n = int(n)
+        if tuple(int(v) for v in shape) != (m, n):
+            raise ValueError(f"{name}: {what} is {tuple(shape)}, the cell has {m} x {n} elements")
+        if int(nu) < 1 or int(coarse_sweeps) < 1 or int(batch) < 1 or int(check_every) < 1:
+            raise ValueError(f"{name}: nu, coarse_sweeps, batch and check_every must be at least 1")
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name} needs the MI355X (there is no CPU fallback for the HIP path)")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        _lib.lib()
+        self.m, self.n, self.B, self.dtype = m, n, int(batch), dtype
+        self.size, self.h, self.omega = float(size), float(size) / n, float(omega)
+        self.nu, self.coarse_sweeps = int(nu), int(coarse_sweeps)
+        self.use_graph, self.check_every = bool(graph), int(check_every)
+        self.levels = [_TorusLevel(lm, ln, self.B, dtype, self.device) for lm, ln in coarse_shapes(m, n)]
         L0 = self.levels[0]
         self.r = L0.f  # the preconditioner's right-hand side buffer is the residual
         self._x, self.p, self.y = (torch.zeros_like(L0.f) for _ in range(3))
@@ -149,19 +152,18 @@ class PeriodicPCGSolver:
         rec = _lib.launch(name, **kw)
         _lib.call(rec[0], self.dtype, *rec[1], self._stream())
 
+    # the three launches of the operator: what a solver on another operator (feanet_amd.coef) replaces
+    def _stencil(self, L):
+        return dict(pid=L.pid.data_ptr(), ldp=L.ldp, ktab=self.ktab.data_ptr())
+
     def _sweep(self, L, u, out):
         self._call("per_sweep", u=None if u is None else u.data_ptr(), f=L.f.data_ptr(), out=out.data_ptr(),
-                   pid=L.pid.data_ptr(), ldp=L.ldp, ktab=self.ktab.data_ptr(), omd=self.omd.data_ptr(), B=self.B,
-                   **L.geom())
+                   **self._stencil(L), omd=self.omd.data_ptr(), B=self.B, **L.geom())
 
     def _residual_restrict(self, L, C, u):
         """C.f = R (L.f - K u)"""
-        self._call("per_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), pid=L.pid.data_ptr(),
-                   ldp=L.ldp, ktab=self.ktab.data_ptr(), B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
-
-    def _floor(self):
-        """solved_floor of this solver's operator"""
-        return solved_floor(self.prop, self.h, self.m, self.n, self.dtype)
+        self._call("per_residual_restrict", u=u.data_ptr(), f=L.f.data_ptr(), fc=C.f.data_ptr(), **self._stencil(L),
+                   B=self.B, **L.geom(), ldc=C.ld, bstridec=C.bs)
 
     def _sweeps(self, L, u, count):
         """count sweeps from u (None: the zero guess), ping-pong between L.a and L.b -> the buffer of the result"""
@@ -199,11 +201,12 @@ class PeriodicPCGSolver:
         s = self._reduce(v) if total is None else total
         v.sub_((s / float(self.m * self.n)).to(self.dtype)[:, None, None])
 
+    def _apply(self, L, p, y, part):
+        self._call("per_apply", p=p.data_ptr(), y=y.data_ptr(), part=part, **self._stencil(L), B=self.B, **L.geom())
+
     def apply(self, p, y, sums=False):
         """y = K p on torus buffers; sums: also (p . y, sum y) per sample as a [B, 2] float64 view."""
-        L0 = self.levels[0]
-        self._call("per_apply", p=p.data_ptr(), y=y.data_ptr(), part=self.part.data_ptr() if sums else None,
-                   pid=L0.pid.data_ptr(), ldp=L0.ldp, ktab=self.ktab.data_ptr(), B=self.B, **L0.geom())
+        self._apply(self.levels[0], p, y, self.part.data_ptr() if sums else None)
         if sums:
             self._final(2 * self.B)
             return self.sums.view(self.B, 2)
@@ -275,7 +278,7 @@ class PeriodicPCGSolver:
         self.rr0.copy_(torch.sqrt(self._reduce(self.r, self.r)))
         self.rn.copy_(self.rr0)
         self.thresh.copy_(self.rr0 * float(rtol))
-        self.flag.copy_((self.rr0 <= self._floor()).to(torch.int64))
+        self.flag.copy_((self.rr0 <= solved_floor(self.kmax, self.h, m, n, self.dtype)).to(torch.int64))
         self.rz_old.fill_(float("inf"))
         self.iters.zero_()
         self.hist[0] = self.rr0
@@ -314,16 +317,17 @@ class PeriodicPCGSolver:
         return U
 
     def _framed(self):
+        """(the framed copy of the unwrapped field, its geometry (B, H, W, ld, bstride))"""
         from . import flux as fx
-        from .flux import coefficients
-        framed, B, H, W, ld, bs = fx._framed_copy(self.unwrapped(), "u")
-        return framed, (B, H, W, ld, bs), coefficients(self.prop)
+        framed, *geom = fx._framed_copy(self.unwrapped(), "u")
+        return framed, tuple(geom)
 
     def flux(self, fields=True):
         """Element fluxes, their means, the mean gradient and the energy of the unwrapped field, as
         MultigridSolver.flux; no host synchronisation."""
         from . import flux as fx
-        framed, geom, (k0, k1) = self._framed()
+        framed, geom = self._framed()
+        k0, k1 = fx.coefficients(self.prop)
         return fx.flux_framed(framed.data_ptr(), self.dtype, self.device, *geom, phase=self.levels[0].image, k0=k0,
                               k1=k1, h=self.h, fields=fields)
 
@@ -331,6 +335,6 @@ class PeriodicPCGSolver:
         """The energy forms between samples pair[0] and pair[1] of the unwrapped field, as
         MultigridSolver.energy_forms; no host synchronisation."""
         from . import flux as fx
-        framed, geom, _ = self._framed()
+        framed, geom = self._framed()
         return fx.pair_forms(framed.data_ptr(), self.dtype, self.device, self.B, geom, pair, self.levels[0].image,
                              fields, "PeriodicPCGSolver.energy_forms")

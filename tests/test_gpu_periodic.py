@@ -15,7 +15,8 @@ import phase_ref as pr
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(2, 2), (4, 6), (6, 10), (12, 16), (20, 66), (32, 130)]
+# (6, 258): a second strip in fp32 too (256 columns), so lane 63 loads its right neighbour
+EVEN = [(2, 2), (4, 6), (6, 10), (12, 16), (20, 66), (32, 130), (6, 258)]
 SUFS = ["f64", "f32"]
 DT = {"f32": torch.float32, "f64": torch.float64}
 NP = {"f32": np.float32, "f64": np.float64}
@@ -23,6 +24,9 @@ U = {"f32": 2.0 ** -24, "f64": 2.0 ** -53}
 PROP = (1, 20)
 B = 3
 RTOL = 1e-10
+# the smallest m at n = 16 for which fea_per_parts shows more than one row task (the same for both types: one strip)
+M_TASKS = next(m for m in range(2, 64) if pf.parts(m, 16, 8) > 1 and pf.parts(m, 16, 4) > 1)
+SHAPES = EVEN + [(5, 7), (M_TASKS, 16)]
 
 
 # ----------------------------------------------------------------------------- torus buffers
@@ -205,7 +209,7 @@ def test_sweep(m, n, suf):
 
 
 @pytest.mark.parametrize("suf", SUFS)
-@pytest.mark.parametrize("m, n", SHAPES)
+@pytest.mark.parametrize("m, n", EVEN)
 def test_residual_restrict_and_prolong(m, n, suf):
     """fc = R (f - K u): S = R (|f| + S_K), 9 + 2 terms of the residual and 9 of the restriction; u += R^T ec:
     S = |u| + R^T |ec|, at most four additions, the weight and the sum."""

@@ -23,8 +23,11 @@ sys.path.insert(0, os.path.join(HERE, "..", "multigrid-feanet_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from feanet_amd import _lib  # noqa: E402
+from feanet_amd.coef import CoefPeriodicPCGSolver  # noqa: E402
 from feanet_amd.dd import DDSolver, Kernels, LocalGroup  # noqa: E402
 from feanet_amd.pcg import PCGSolver  # noqa: E402
+from feanet_amd.periodic import PeriodicPCGSolver  # noqa: E402
 from feanet_amd.solver import MultigridSolver  # noqa: E402
 from tools.dd_projection import PackComm  # noqa: E402
 
@@ -102,6 +105,48 @@ def pcg(label, n, precond):
     emit(label, "history", np.stack([np.asarray(h) for h in p.history()]))
 
 
+def torus(label, family, m, n, dtype, B=3):
+    """every torus kernel of one family on seeded fields (through the solver's own launches, so on its operator data),
+    then x and the residual history of 4 iterations of solve()"""
+    rng = np.random.default_rng([m, n])
+    kw = dict(rows=m, dtype=dtype, batch=B, graph=False)
+    if family == "per":
+        s = PeriodicPCGSolver(n, phase=(rng.random((m, n)) < 0.4).astype(np.uint8), prop=(1, 20), **kw)
+        op = s._stencil
+    else:
+        s = CoefPeriodicPCGSolver(n, coef=np.exp(rng.standard_normal((m, n))), **kw)
+        op = s._field
+    L = s.levels[0]
+
+    def field(ref):
+        buf = torch.zeros_like(ref)
+        rows, cols = buf.shape[1], n if buf.shape[1] == m else n // 2
+        buf[..., :cols] = torch.from_numpy(rng.standard_normal((B, rows, cols))).to(dtype).cuda()
+        return buf
+
+    u, out = field(L.f), torch.zeros_like(L.f)
+    L.f.copy_(field(L.f))
+    s._sweep(L, u, out)
+    emit(label, "sweep", out)
+    s._sweep(L, None, out)
+    emit(label, "sweep0", out)
+    emit(label, "apply", out, s.apply(u, out, sums=True))
+    if family == "per":
+        emit(label, "reduce", s._reduce(u, L.f).clone(), s._reduce(u))
+    if len(s.levels) > 1:
+        C = s.levels[1]
+        for what, ptr in (("restrict", u.data_ptr()), ("restrict0", None)):
+            s._call(family + "_residual_restrict", u=ptr, f=L.f.data_ptr(), fc=C.f.data_ptr(), **op(L), B=B,
+                    **L.geom(), ldc=C.ld, bstridec=C.bs)
+            emit(label, what, C.f)
+        if family == "per":
+            s._call("per_prolong_add", ec=field(C.f).data_ptr(), u=u.data_ptr(), B=B, **L.geom(), ldc=C.ld,
+                    bstridec=C.bs)
+            emit(label, "prolong", u)
+    x = s.solve(field(L.f)[..., :n], rtol=0.0, max_iters=4)
+    emit(label, "solve4", x, np.stack(s.history))
+
+
 def main():
     name = {T32: "fp32", T64: "fp64"}
     for dtype in (T64, T32):
@@ -141,6 +186,13 @@ def main():
             L0 = d.local.levels[0]
             emit(f"dd rank {rank} of {grid[0]} x {grid[1]} {n + 1}^2 Ld={Ld} {'+'.join(sends) or 'no _send'}", "vcycle3",
                  L0.view(L0.buf(d._state)), d._gsend if getattr(d, "_gsend", None) is not None else np.zeros(0))
+
+    # the smallest m at n = 16 with more than one row task (the same for both types: one strip)
+    m_tasks = next(m for m in range(2, 64) if min(_lib.lib().fea_per_parts(m, 16, e) for e in (4, 8)) > 1)
+    for family in ("per", "coef"):
+        for dtype in (T64, T32):
+            for m, n in ((6, 258), (m_tasks, 16), (32, 130)):
+                torus(f"torus {family} {m} x {n} {name[dtype]} B=3", family, m, n, dtype)
 
     text = "\n".join(OUT) + "\n"
     if len(sys.argv) > 1:
